@@ -15,7 +15,17 @@ raytracer.rs:65), default test light, RGBA8 output.  One step = one frame:
 
 value = W*H primary rays per frame * K frames / (max over ranks of the timed wall time), in
 millions.  The scene blob and texture are uploaded before the timed region (inputs resident in
-HBM).  rank 0 prints ONE JSON line with two extra objects:
+HBM).  rank 0 prints ONE JSON line.
+
+A plain run (``python bench.py --gpus 1 --steps K --warmup W``) does only what `value` needs: set-up
+(upload, the scene's specialised kernels, settle), the warm-up steps, the K timed steps, and the line
+(`roofline` restates this run's kernel time against committed counts: it takes no run of its own).
+``--dump-outputs DIR`` then writes the frame(s) the last timed step rendered as DIR/<name>.npy
+(dump_outputs).  ``--full`` adds everything else the benchmark measures or checks, after the timed
+region or in contexts of their own: the frame-buffer check against a single-launch render, the
+other half of the scaling picture (`inflight4` / `single_frame`), the generic kernels' frame time
+(`specialisation.generic_ms_per_frame`), anim120's per-frame kernel times where the timed region
+has no events, and `cpu_baseline`.  The line's two extra objects:
 
 * roofline -- the render kernel against the FP64 vector roofline (this path has no dense
   contraction and ~0.1 B/flop, see DESIGN.md "Roofline"): algorithmic flops per launch (the
@@ -24,7 +34,7 @@ HBM).  rank 0 prints ONE JSON line with two extra objects:
   the launch stream; traffic = HBM bytes per launch from the committed rocprofv3 PMC summary
   (profiles/) when it exists for this workload, else null.  ``roofline_hbm`` restates the same
   launch against HBM bandwidth, as the north star asks.
-* cpu_baseline -- the CPU oracle (a faithful C restatement of the reference loop; the Rust
+* cpu_baseline (``--full``) -- the CPU oracle (a faithful C restatement of the reference loop; the Rust
   reference cannot be built here) timed on this host on rank 0 at N=1 only, on every core this
   process may run on (sched_getaffinity, capped by the cgroup CPU quota), as the reference's
   threadpool is sized to num_cpus (src/raydebugger/gui.rs:49-51), plus a 1-thread sample.
@@ -96,10 +106,17 @@ def parse():
                          "ranks on one device).  The line carries no value")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline threads (0 = every core available to this process)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what `value` does not need: the frame-buffer check against a single-launch "
+                         "render, the extra phase (inflight4 / single_frame), the generic kernels' frame time, "
+                         "anim120's untimed step with per-frame events, and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step rendered (rank 0's frame; anim120: "
+                         "rank 0's frames) as DIR/<name>.npy, float32 (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the extra phase after the timed region (N = 1: 4 frames in flight; N > 1: one "
-                         "frame at a time), which reports the other half of the scaling picture")
+                    help="--full without the extra phase after the timed region (N = 1: 4 frames in flight; "
+                         "N > 1: one frame at a time), which reports the other half of the scaling picture")
     ap.add_argument("--inflight", type=int, default=0,
                     help="frames whose renders may overlap, each on a stream with its own hardware queue "
                          "(0 = 1 at N = 1, so the roofline's kernel time and the rocprof trace are of one launch "
@@ -396,7 +413,7 @@ def main():
         rend.spec_wait()                                  # setup: before the settle / warmup / timed steps
         spec_ms = round((time.perf_counter() - t_up) * 1e3, 1)
         spec = {"request_to_loaded_ms": spec_ms, "first_frame_ms": first_frame_ms, "first_frame_kernel": first_kernel,
-                "generic_ms_per_frame": generic_frame_ms(T, text, t, W, H, depth, local, dev) if world == 1 else None,
+                "generic_ms_per_frame": generic_frame_ms(T, text, t, W, H, depth, local, dev) if world == 1 and a.full else None,
                 "note": "RT_OPT_SPECIALIZE 1 (the library default) compiles in a background pool: upload and the first "
                         "frames return at once on the generic kernels, the specialised kernels take over when loaded "
                         "(request_to_loaded_ms, the compile plus the load; ~0 with the on-disk or comgr cache warm)"}
@@ -543,16 +560,20 @@ def main():
                  [reg[0].elapsed_time(reg[1]) / a.steps] if region else [elapsed * 1e3 / a.steps])
     mean_kernel_ms = sum(kernel_ms) / len(kernel_ms)
     rows_per_rank = None
-    # outside the timed region: every frame buffer holds one of the last frames (assembled, at
-    # N > 1); each must equal a single-launch render of the whole frame on the default stream
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"frame": frames[(a.warmup + a.steps - 1) % nbuf]})
+    # --full, outside the timed region: every frame buffer holds one of the last frames (assembled,
+    # at N > 1); each must equal a single-launch render of the whole frame on the default stream
     # (catches any stream-ordering or buffer-reuse mistake)
-    whole = rend.render_rows(0, H, max_depth=depth)
-    torch.cuda.synchronize(dev)
-    used = min(nbuf, a.warmup + a.steps)
-    bad = [b for b in range(used) if not torch.equal(frames[b], whole)]
-    if bad:
-        raise SystemExit(f"rank {rank}: frame buffer(s) {bad} differ from the single-launch render")
-    frame_check = f"all {used} frame buffers == single-launch render" + (", on every rank" if multi else "")
+    whole = frame_check = None
+    if a.full:
+        whole = rend.render_rows(0, H, max_depth=depth)
+        torch.cuda.synchronize(dev)
+        used = min(nbuf, a.warmup + a.steps)
+        bad = [b for b in range(used) if not torch.equal(frames[b], whole)]
+        if bad:
+            raise SystemExit(f"rank {rank}: frame buffer(s) {bad} differ from the single-launch render")
+        frame_check = f"all {used} frame buffers == single-launch render" + (", on every rank" if multi else "")
     if multi:
         counts = [None] * world
         dist.all_gather_object(counts, sum(y1 - y0 for y0, y1 in mine))
@@ -560,19 +581,19 @@ def main():
     busy_ms = mean_kernel_ms if K == 1 else elapsed * 1e3 / a.steps
 
     # One definition of scaling (DESIGN.md "Multi-GPU"): the line carries BOTH the latency and the
-    # throughput figure at every N, measured after the timed region (they are not `value`):
+    # throughput figure at every N, measured after the timed region under --full (they are not `value`):
     # N = 1: `inflight4` -- the same frames with 4 in flight on own-queue streams (the N > 1 default);
     # N > 1: `single_frame` -- one frame at a time, fully serialised, with events on the launch stream
     #        around the rank's band render, the all-gather (as seen by the assembly: render end ->
     #        gather done, so it includes waiting for the slowest rank) and the assembly kernel.
     extra_steps = max(4, min(a.steps, 20))
     single = infl = None
-    if multi and overlap and not a.no_extra:
+    if a.full and multi and overlap and not a.no_extra:
         fl0 = load_flops(scene, W, H, t, depth)
         single = single_frame_phase(a, T, rend, dist, D, stream, dev, slots[0], gath[0], frames[0], whole,
                                     (y_first, band_rows, pitch, n_bands), H, W, world, layout, band, depth,
                                     rehearse, extra_steps, fl0["row_flops"] if fl0 else None)
-    elif not multi and K == 1 and not a.no_extra:
+    elif a.full and not multi and K == 1 and not a.no_extra:
         infl = inflight_phase(T, rend, stream, dev, frames[0], whole, H, W, depth, local, 4, max(20, a.steps),
                               a.settle_ms)
     if rank == 0 and a.png:
@@ -670,7 +691,7 @@ def main():
             single["value"] = round(W * H / (single["ms_per_step"] * 1e-3) / 1e6, 2)
     if infl is not None:
         line["inflight4"] = infl
-    if world == 1 and not multi and not a.no_cpu_baseline:
+    if a.full and world == 1 and not multi and not a.no_cpu_baseline:
         cb = cpu_baseline(text, W, H, t, depth, a.cpu_threads)
         cb["gpu_over_cpu"] = round(line["value"] / cb["value"], 1)
         line["cpu_baseline"] = cb
@@ -680,6 +701,27 @@ def main():
         h.close()
     if multi:
         dist.destroy_process_group()
+
+
+DUMP_MAX_PIXELS = 1 << 21           # x 4 channels x 4 bytes = 32 MiB of float32 per array
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each RGBA8 output the timed path's last step produced (a device tensor of
+    shape [..., 4], as the caller of the render receives it) to `path`/<name>.npy as float32 channel
+    values 0..255, one row per pixel.  An output of more than DUMP_MAX_PIXELS pixels is written as a
+    fixed sample of that many of its pixels (numpy default_rng(DUMP_SEED), indices ascending), so two
+    builds' files hold the same pixels and compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        px = x.reshape(-1, x.shape[-1])
+        if px.shape[0] > DUMP_MAX_PIXELS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(px.shape[0], DUMP_MAX_PIXELS, replace=False))
+            px = px[torch.from_numpy(idx).to(px.device)]
+        np.save(os.path.join(path, name + ".npy"), px.cpu().numpy().astype(np.float32))
 
 
 def generic_frame_ms(T, text, t, W, H, depth, local, dev, frames=10):
@@ -1024,8 +1066,9 @@ def anim_main(a, json_out, rank, world, local, dev, multi, rehearse=False):
     # one stream: an event pair per frame gives the frames' kernel times; several streams: no events in
     # the timed region (each timed event costs its stream ~5 us, profiles/r02dc_launch_events.txt, and
     # the roofline is taken over wall time then) -- the per-frame times come from one untimed step after
+    # the timed region, under --full only
     evs = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in mine]
-           for _ in range(a.steps if K == 1 else 1)]
+           for _ in range(a.steps if K == 1 else 1 if a.full else 0)]
     if multi:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -1040,21 +1083,25 @@ def anim_main(a, json_out, rank, world, local, dev, multi, rehearse=False):
         e = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else dev)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
-    if K > 1:
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"frames": torch.stack(outs)})
+    if K > 1 and a.full:
         step(evs[0])                                      # untimed: the frames' kernel times
         torch.cuda.synchronize(dev)
     per_frame = [sum(evs[i][j][0].elapsed_time(evs[i][j][1]) for i in range(len(evs))) / len(evs)
-                 for j in range(len(mine))]
-    # outside the timed region: every owned frame buffer == a single-launch render of its frame
-    bad = []
-    for j, r in enumerate(rends):
-        whole = r.render_rows(0, H, max_depth=depth)
-        torch.cuda.synchronize(dev)
-        if not torch.equal(outs[j], whole):
-            bad.append(mine[j])
-    if bad:
-        raise SystemExit(f"rank {rank}: frame buffer(s) of frames {bad} differ from the single-launch render")
-    frame_check = f"all {len(mine)} frame buffers == single-launch render" + (", on every rank" if multi else "")
+                 for j in range(len(mine))] if evs else None
+    # --full, outside the timed region: every owned frame buffer == a single-launch render of its frame
+    frame_check = None
+    if a.full:
+        bad = []
+        for j, r in enumerate(rends):
+            whole = r.render_rows(0, H, max_depth=depth)
+            torch.cuda.synchronize(dev)
+            if not torch.equal(outs[j], whole):
+                bad.append(mine[j])
+        if bad:
+            raise SystemExit(f"rank {rank}: frame buffer(s) of frames {bad} differ from the single-launch render")
+        frame_check = f"all {len(mine)} frame buffers == single-launch render" + (", on every rank" if multi else "")
     frames_per_rank = None
     if multi:
         counts = [None] * world
@@ -1104,9 +1151,9 @@ def anim_main(a, json_out, rank, world, local, dev, multi, rehearse=False):
             "streams": K,
             "achieved_basis": "kernel event time" if K == 1 else "step wall time (frames overlap on the streams; "
                               "kernel_ms_*: one untimed step with events, overlapped)",
-            "kernel_ms_mean": round(sum(per_frame) / len(per_frame), 4),
-            "kernel_ms_min": round(min(per_frame), 4),
-            "kernel_ms_max": round(max(per_frame), 4),
+            "kernel_ms_mean": round(sum(per_frame) / len(per_frame), 4) if per_frame else None,
+            "kernel_ms_min": round(min(per_frame), 4) if per_frame else None,
+            "kernel_ms_max": round(max(per_frame), 4) if per_frame else None,
             "issue": issue_model(a.config, 1, "contiguous", busy_frame_ms),
         }),
         "rays": rays_line(fl, F * W * H * a.steps / elapsed),
@@ -1124,7 +1171,7 @@ def anim_main(a, json_out, rank, world, local, dev, multi, rehearse=False):
     if rehearse:
         line.update({"metric": "one-GPU rehearsal of the N-rank animation (not a measurement)", "value": None,
                      "vs_baseline": None, "roofline": None, "rays": None})
-    if world == 1 and not multi and not a.no_cpu_baseline:
+    if a.full and world == 1 and not multi and not a.no_cpu_baseline:
         from oracle import oracle as O
         cores, model, aff, quota = host_cpus()
         threads = a.cpu_threads or cores

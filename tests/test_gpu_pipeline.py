@@ -30,7 +30,7 @@ def test_collective_pipeline_frames_in_flight(gather, layout):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--force-collective",
+           "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--full", "--force-collective",
            "--inflight", "4", "--steps", "12", "--warmup", "3", "--settle-ms", "0", "--no-cpu-baseline",
            "--gather", gather, "--layout", layout]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=240)
@@ -53,7 +53,7 @@ def test_rehearsal_n_ranks_on_one_gpu(world, inflight, layout):
     frame, and EVERY rank checks every frame buffer against its own single-launch render."""
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--rehearse-one-gpu",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full", "--rehearse-one-gpu",
            "--steps", "4", "--warmup", "2", "--settle-ms", "0", "--layout", layout, "--inflight", str(inflight)]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -76,7 +76,7 @@ def test_rehearsal_animation_ranks_on_one_gpu(world):
     render of that frame."""
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--rehearse-one-gpu",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full", "--rehearse-one-gpu",
            "--config", "anim120", "--steps", "2", "--warmup", "1", "--settle-ms", "0", "--streams", "2"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
