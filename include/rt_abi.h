@@ -295,10 +295,20 @@ int rt_ctx_synchronize(rt_ctx* ctx);
  * value again after a failure retries the compile.  Launches whose kernel has no specialised form
  * (wavefront, refraction deferred, RT_OPT_FAST_CLAMP 0 on a min/max-clamp scene) keep the generic
  * kernels.
+ * RT_OPT_TILE_MASKS: the single-scene specialised kernels of reflection-only scenes can take a table of
+ * per-tile object masks (which objects the tile's primary rays, its floor hits' shadow rays and their
+ * reflections can reach at all, decided once per upload and launch geometry by one small kernel on the
+ * launch's stream, no host synchronisation), so their walks skip provably empty box tests.  The masked
+ * megakernel's walks cost a few percent more each, so the program also holds its megakernel without the
+ * mask operand, and a launch takes one or the other: 1 (default) the primary-ray kernel always takes the
+ * table, the megakernel where the geometry's tile-order calibration found the launch throughput-bound
+ * (costliest tile <= the work per wave slot; launches without a measured order take none); 2 every launch
+ * that can; 0 none (the mask-free kernels: the walks of a library without masks).  Same pixels.
+ * rt_ctx_kernel_info says whether the last launch took masks.
  * Option 7 is retired (round 4's tail kernel, measured slower than the launch it shortened). */
 typedef enum rt_option {
   RT_OPT_KERNEL = 0, RT_OPT_TIMING = 1, RT_OPT_TILE_ORDER = 2, RT_OPT_FAST_CLAMP = 3, RT_OPT_WAVEFRONT_CAP = 4,
-  RT_OPT_WAVEFRONT_PAIRS = 5, RT_OPT_SPECIALIZE = 6
+  RT_OPT_WAVEFRONT_PAIRS = 5, RT_OPT_SPECIALIZE = 6, RT_OPT_TILE_MASKS = 8
 } rt_option;
 typedef enum rt_kernel_choice {
   RT_KERNEL_AUTO = 0, RT_KERNEL_MEGA = 1, RT_KERNEL_DEFERRED = 2, RT_KERNEL_WAVEFRONT = 3
@@ -308,6 +318,19 @@ int rt_ctx_set_option(rt_ctx* ctx, int32_t option, int32_t value);
  * RT_OPT_SPECIALIZE is on (compiling in the background, failed, scene too large) -- or the specialised
  * program's hash, mode, compile time, compiler and resources, and which kernel the last row launch took. */
 int rt_ctx_kernel_info(rt_ctx* ctx, char* buf, size_t cap);
+/* Tile masks (RT_OPT_TILE_MASKS; tests, debugging).  A band launch (y_first, band_rows, band_pitch,
+ * n_bands as rt_render_row_bands; a contiguous range [y0, y1) is (y0, y1 - y0, y1 - y0, 1)) has
+ * ceil(width / 8) * ceil(rows / 8) tiles, row-major, of 6 words each: prim, shadow[0..3], refl; bit o
+ * = object o.  A clear bit says that no ray of that class from the tile can have an accepted hit in
+ * object o's culling box.  rt_ctx_tile_masks copies the uploaded scene's table for that geometry from
+ * the device (computing it first if no launch has; whatever the option says), rt_scene_tile_masks
+ * evaluates the same predicate on the host.  Both write min(cap_words, 6 * tiles) words (whole tiles
+ * only on the host).  *n_tiles = the tile count; info = { tiles, the mask plane's object index or -1,
+ * the bit set of objects with a finite box, 1 if the scene takes masks at all (<= 32 objects) }. */
+int rt_ctx_tile_masks(rt_ctx* ctx, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
+                      uint32_t* words, size_t cap_words, uint32_t* n_tiles);
+int rt_scene_tile_masks(const rt_scene* scene, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch,
+                        uint32_t n_bands, uint32_t* words, size_t cap_words, int32_t info[4]);
 /* Block until the context's specialised program (RT_OPT_SPECIALIZE) is loaded, at most timeout_ms
  * (< 0: no limit).  RT_OK: loaded, or nothing to wait for (option off, scene too large); RT_PENDING:
  * the limit passed first; a negative status: the compile failed or the guard refused it (the

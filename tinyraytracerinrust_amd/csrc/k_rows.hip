@@ -116,6 +116,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   RT_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;   // NULL = the device's default stream
   (void)spec_poll(c);                     // the scene-specialised kernels, once their background compile is done
+  c->last_masked = false;
   const bool dev_out = is_device_ptr(out);
   uint8_t* target = (uint8_t*)out;
   size_t tstride = stride;
@@ -191,6 +192,21 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   else if (order) deferred = slot->deferred;
   else if (calibrate) deferred = false;                       // calibrate on the megakernel
   else deferred = n_tiles < RT_ORDER_MIN_TILES || (!c->tile_order && n_tiles < RT_DEFERRED_MAX_TILES);
+  // The launch geometry's tile masks: the single-scene reflection-only programs' megakernel and
+  // primary-ray kernel read them (a family program, the other modes and the deferred kernel take none).
+  // A table that is new since the upload is filled here, AHEAD of the timing event: rt_ctx_last_kernel_ms
+  // reports the render kernel alone.  (The kernel choice below is restated for it.)
+  const uint32_t* mask_table = nullptr;
+  if (c->spec_mod && !refr && c->spec_mode == RT_MODE_REFL && !c->spec_family && c->dev.n_objects <= 32 &&
+      (c->dev.colour_fast != 0 && c->fast_clamp) == c->spec_fc) {
+    // RT_OPT_TILE_MASKS 1: the primary-ray kernel always takes the table (its one walk per pixel only gains);
+    // the megakernel where the geometry's calibration found the launch throughput-bound (OrderSlot::masks_pay).
+    // A launch without a measured order (too small, calibrating, tile order off) takes none.  2: every launch.
+    const bool prim0 = max_depth == 0 && dmode != 1 && c->spec_prim[f64 ? 1 : 0][calibrate ? 1 : 0];
+    const bool want = c->tile_masks == 2 || (c->tile_masks == 1 && (prim0 || (order && slot->masks_pay)));
+    if (want && (prim0 || (!deferred && c->spec_rows[f64 ? 1 : 0][calibrate ? 1 : 0])))
+      RT_TRY(launch_masks(c, st, a0, a1, a2, a3, n_tiles, &mask_table));
+  }
   if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
   // the row kernels carry the context's completion event for this stream as their stop event
   hipEvent_t mev = nullptr;
@@ -252,9 +268,23 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   }
   c->last_kernel = prim ? "primary-ray (specialised)"
                         : deferred ? (sfn ? "deferred (specialised)" : "deferred") : (sfn ? "megakernel (specialised)" : "megakernel");
+  // Two encodings in these kernels name an object in fewer bits than an int: the wave pool's frames hold
+  // the hit object in ONE BYTE (rt_device.h RT_POOL_OBJ_INDEX: chain kernels, and reflection-only builds
+  // with a pool) and the tile masks hold one BIT per object in a 32-bit word (rt_tilemask.h).  Both
+  // limits are checked here, where such a kernel is chosen: a pooled kernel is refused beyond 256
+  // objects (flatten already keeps such scenes out of the chain mode), a masked one takes no table
+  // beyond 32 (put_mask_scene marks such scenes, and the specialised programs stop at 32 objects too).
+  const bool pooled = !deferred && (mode == RT_MODE_CHAIN || (mode == RT_MODE_REFL && RT_LDS_POOL_REFL > 0));
+  if (pooled && RT_POOL_OBJ_INDEX && c->dev.n_objects > 256)
+    return fail(RT_ERR_UNSUPPORTED, "a pooled kernel for a scene of %d objects (one-byte object index)", c->dev.n_objects);
+  const uint32_t* masks = sfn && !deferred && mode == RT_MODE_REFL ? mask_table : nullptr;
+  c->last_masked = masks != nullptr;
+  // a megakernel launch without a table runs the program's mask-free megakernel (spec.hip kind 3)
+  if (sfn && !prim && !deferred && !masks && c->spec_rows_nm[f64 ? 1 : 0][calibrate ? 1 : 0])
+    sfn = c->spec_rows_nm[f64 ? 1 : 0][calibrate ? 1 : 0];
   if (sfn) {
     void* kargs[] = {&c->dev, (void*)&a0, (void*)&a1, (void*)&a2, (void*)&a3, &max_depth, &target, &tstride,
-                     (void*)&order, &cost, (void*)&rgbi};
+                     (void*)&order, &cost, (void*)&rgbi, (void*)&masks};
     // hipExtModuleLaunchKernel takes the global work size in work-items (grid x 64)
     RT_HIP(hipExtModuleLaunchKernel(sfn, grid.x * 64u, 1, 1, 64, 1, 1, 0, st, kargs, nullptr, nullptr, mev, 0));
   }
@@ -308,6 +338,17 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
     bool tail_bound = false;
     // wave slots of the calibrated (mega)kernel on this device
     const double slots = (double)c->n_cu * 4.0 * (double)(!refr ? RT_WAVES_PER_EU_NOREFR : c->dev.ray_chains ? RT_WAVES_PER_EU_CHAIN : RT_WAVES_PER_EU);
+    // Tile masks (RT_OPT_TILE_MASKS 1): the masked megakernel removes work from the tiles whose walks are
+    // provably empty (floor, sky) and costs every walk of every tile a few percent.  A launch that fills the
+    // GPU many times over gains the difference (4K globes: -2.8 %); one whose time is set by its costliest
+    // tiles -- deep reflection chains, whose walks beyond depth 1 take no mask -- only pays (1080p globes
+    // d5: +1.4 %).  The same measure as the deferred kernel's choice below decides: costliest tile against
+    // the work per wave slot.
+    {
+      uint64_t sum = 0, mx = 0;
+      for (uint32_t v : h_cost) { sum += v; mx = v > mx ? v : mx; }
+      slot->masks_pay = (double)mx <= (double)sum / slots;
+    }
     // With the scene-specialised megakernel loaded for these launches its costliest tiles finish so
     // much sooner that the deferred kernel no longer pays anywhere: lone 4K rank shares at N = 4 / 8
     // (tail ratios 1.6 / 3.0) 0.109 / 0.098 ms against 0.156 / 0.117 ms deferred, 1080p d5 (ratio 1.6)

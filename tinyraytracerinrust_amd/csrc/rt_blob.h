@@ -44,6 +44,8 @@ using __hip_internal::uint64_t;
 #ifndef RT_TILE_W
 #define RT_TILE_W 8
 #endif
+// Per-tile object masks (rt_tilemask.h): words per tile -- prim, shadow[0..3], refl; bit o = object o.
+#define RT_TILEMASK_WORDS 6
 #define RT_MODE_REFL 0
 #define RT_MODE_CHAIN 1
 #define RT_MODE_TREE 2

@@ -60,11 +60,37 @@ struct rt_ctx {
     uint64_t last_use = 0;
     bool deferred = false;            // ordered launches take the deferred-shadow kernel
     int wf_tune = 0;                  // ray-tree scenes, RT_KERNEL_AUTO: 0 not yet timed, 1 megakernel, 2 wavefront
+    bool masks_pay = false;           // the calibration found the launch throughput-bound: the masked megakernel
+                                      // (RT_OPT_TILE_MASKS 1); kept with the order across same-structure uploads
     bool valid = false;               // set once the sorted order is on the device
   };
   static constexpr int RT_ORDER_SLOTS = 8;
   OrderSlot order[RT_ORDER_SLOTS];
   uint64_t use_clock = 0;
+  // Per-tile object masks (rt_tilemask.h, k_masks.hip): one table of RT_TILEMASK_WORDS words per tile
+  // and launch geometry (rows, bands, width: the masks depend on neither depth nor output format, and
+  // launches too small for a tile order take them as well, so the tables have slots of their own
+  // beside the orders').  Unlike a tile order a table depends on the camera and on every object's
+  // position: it is DROPPED ON EVERY UPLOAD and filled again by the first launch of its geometry after
+  // it -- one small kernel on that launch's stream ahead of the render, no host synchronisation.
+  // `ready` is recorded after the fill; launches on other streams wait for it on the device until the
+  // host has seen it complete.
+  struct MaskSlot {
+    int32_t key[5] = {0};             // y_first, band_rows, band_pitch, n_rows, width
+    uint32_t* d_masks = nullptr;
+    size_t n_tiles = 0;
+    uint64_t last_use = 0;
+    hipStream_t fill_stream = nullptr;
+    hipEvent_t ready = nullptr;
+    bool seen_ready = false;
+    bool valid = false;
+  };
+  static constexpr int RT_MASK_SLOTS = 8;
+  MaskSlot masks[RT_MASK_SLOTS];
+  int tile_masks = 1;                   // rt_ctx_set_option(RT_OPT_TILE_MASKS): 0 never, 1 where they pay (OrderSlot::masks_pay), 2 always
+  bool masks_ok = false;                // the uploaded scene has a mask scene in its blob (<= 32 objects)
+  const void* d_mask_scene = nullptr;   // RtTileMaskScene in the blob
+  bool last_masked = false;             // the last row launch passed a mask table (rt_ctx_kernel_info)
   // Scene-specialised row kernels (spec.hip, rt_ctx_set_option(RT_OPT_SPECIALIZE)): hipRTC compiles
   // rt_device.h with this scene's tables as constexpr data, in the background (the library's compile
   // pool); launches take them once they are loaded (spec_poll), the generic kernels until then.
@@ -75,8 +101,11 @@ struct rt_ctx {
   bool spec_deferred = false;           // the program also holds the deferred kernels
   bool spec_fits = false;               // small enough to specialise (RT_SPEC_MAX_OBJECTS / _LEAVES)
   hipModule_t spec_mod = nullptr;       // non-null once the kernels are loaded (null: generic kernels)
-  hipModule_t spec_mods[12] = {};       // one module per specialised kernel, on this context's device
+  hipModule_t spec_mods[16] = {};       // one module per specialised kernel, on this context's device
   hipFunction_t spec_rows[2][2] = {};   // [f64][cal]
+  hipFunction_t spec_rows_nm[2][2] = {};   // [f64][cal]: the megakernel compiled WITHOUT the tile-mask operand (a null
+                                        // table folded at compile time: the walks of a program without masks), for
+                                        // launches that take no table; reflection-only single-scene programs only
   hipFunction_t spec_def[2][2] = {};    // [f64][cal]
   hipFunction_t spec_prim[2][2] = {};   // [f64][cal]: the primary-ray kernel (max_depth 0 launches)
   uint64_t spec_hash = 0;               // FNV-1a of the prelude (kernel info only; caches compare full texts)
@@ -124,6 +153,14 @@ namespace rt {
 // rt_ctx.hip
 void drop_order(rt_ctx::OrderSlot& s);         // frees an order table (hipFree waits for its readers)
 void drop_orders(rt_ctx* c);
+void reset_order_choices(rt_ctx* c);           // a same-structure upload keeps the orders; the ray-tree wavefront choice is timed again
+// k_masks.hip: the tile-mask tables
+void drop_masks(rt_ctx* c);                    // every table (upload, free): hipFree waits for their readers
+int tilemask_plane(const FlatScene& f);        // the mask plane's object index, -1: none
+// The table of the geometry (a0..a3 as launch_wavefront) for a launch on st, filled on st first if it is new
+// since the upload; *table = nullptr when the context takes no masks.
+int launch_masks(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t n_tiles, const uint32_t** table);
+size_t put_mask_scene(const FlatScene& f, std::vector<uint8_t>& blob, bool* ok);   // appends the RtTileMaskScene
 int ensure_scratch(rt_ctx* c, size_t bytes);   // grow-only device scratch for host-pointer launches
 bool is_device_ptr(const void* p);
 // Diagnostic switches read from the environment exist only in a diagnostic build (make diag

@@ -28,6 +28,15 @@ void drop_order(rt_ctx::OrderSlot& s) {
 void drop_orders(rt_ctx* c) {
   for (auto& s : c->order) drop_order(s);
 }
+// What an order slot keeps across an upload of a scene of the same structure: the tile order, and with
+// it the deferred / megakernel choice -- a deferred slot's entries carry its tiles' split (tile | part |
+// log2 parts), so they are no plain permutation another kernel could take, and dropping them would make a
+// host that re-uploads every frame calibrate (a host synchronisation, on the generic kernels) every
+// frame.  What is reset is the one choice that is a measurement apart from the order: wavefront against
+// megakernel for ray-tree scenes (wf_tune), timed again by the next ordered launch of the geometry.
+void reset_order_choices(rt_ctx* c) {
+  for (auto& s : c->order) s.wf_tune = 0;
+}
 
 int ensure_scratch(rt_ctx* c, size_t bytes) {
   if (c->scratch_bytes >= bytes) return RT_OK;
@@ -161,8 +170,11 @@ int rt_ctx_upload(rt_ctx* c, const rt_scene* s) {
   for (size_t x = 0; x < csx.size(); ++x) csx[x] = (((double)x / f.cam.width) - 0.5) * f.cam.aspect;
   for (size_t y = 0; y < csy.size(); ++y) csy[y] = (f.cam.height - 1.0 - (double)y) / f.cam.height - 0.5;
   size_t o_csx = put(blob, csx), o_csy = put(blob, csy);
+  bool masks_ok = false;
+  const size_t o_mask = rt::put_mask_scene(f, blob, &masks_ok);
   RT_HIP(hipSetDevice(c->device));
   RT_TRY(rt::wait_launches(c));       // launches in flight read the blob and may run the specialised modules
+  rt::drop_masks(c);                  // the masks depend on the camera and on every position: never kept
   if (c->d_blob) { (void)hipFree(c->d_blob); c->d_blob = nullptr; }
   c->uploaded = false;
   RT_HIP(hipMalloc(&c->d_blob, blob.size()));
@@ -185,6 +197,8 @@ int rt_ctx_upload(rt_ctx* c, const rt_scene* s) {
   d.texels = b + o_texels;
   d.cam_sx = (const double*)(b + o_csx);
   d.cam_sy = (const double*)(b + o_csy);
+  c->d_mask_scene = b + o_mask;
+  c->masks_ok = masks_ok;
   d.n_objects = (int32_t)f.objects.size();
   d.n_lights = (int32_t)f.lights.size();
   d.n_leaves = (int32_t)f.leaves.size();
@@ -217,7 +231,10 @@ int rt_ctx_upload(rt_ctx* c, const rt_scene* s) {
   // tile order renders the same pixels, the old one is near the new costs, and the first launch after
   // the upload takes an ordered (non-calibrating) kernel -- the specialised one, whose programs have no
   // calibration variant at the default level (a calibrating launch would run the generic kernels).
+  // The ray-tree scenes' wavefront / megakernel choice is measured again (reset_order_choices); the tile
+  // masks, which depend on the camera and on every position, were dropped above whatever the structure.
   if (!(c->spec_flat && rt::same_structure_flat(*c->spec_flat, f))) drop_orders(c);
+  else rt::reset_order_choices(c);
   // the scene-specialised programs (spec.hip): requested from the compile pool, loaded by the first
   // launch after they are ready; the generic kernels render until then.  Only the flags are computed
   // here -- the program text (and a family lookup) only when the option is on and the scene fits.
@@ -253,6 +270,7 @@ int rt_ctx_kernel_info(rt_ctx* c, char* buf, size_t cap) {
     s = "generic (librt_mi355x.so)";
   }
   s += std::string("; last launch: ") + c->last_kernel;
+  s += c->last_masked ? "; tile masks: on" : "; tile masks: off";
   snprintf(buf, cap, "%s", s.c_str());
   return RT_OK;
 }
@@ -292,6 +310,11 @@ int rt_ctx_set_option(rt_ctx* c, int32_t option, int32_t value) {
     rt::spec_drop(c);
     c->spec_on = value;
     if (c->uploaded) rt::spec_prepare(c, retry);   // a scene family registered since the upload may hold it
+    return RT_OK;
+  }
+  if (option == RT_OPT_TILE_MASKS) {
+    if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "RT_OPT_TILE_MASKS value %d", value);
+    c->tile_masks = value;               // the tables stay: launches just stop (or start) passing them
     return RT_OK;
   }
   if (option == RT_OPT_WAVEFRONT_PAIRS) {
@@ -371,6 +394,7 @@ void rt_ctx_free(rt_ctx* c) {
   if (c->wfr) (void)hipFree(c->wfr);
   if (c->wfp) (void)hipFree(c->wfp);
   drop_orders(c);
+  rt::drop_masks(c);
   rt::spec_drop(c);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);

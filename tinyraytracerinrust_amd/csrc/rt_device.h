@@ -639,12 +639,14 @@ __device__ __forceinline__ float cull_tmax_f(double t) { return (float)cull_tmax
 // The traversals' culling ray and tests, f32 (above) or f64 (box_may_hit)
 typedef CullRayF CullR;
 typedef float CullT;
+#define RT_CULL_NEVER() CullRayF{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), 0.0f, 0.0f, 0.0f}
 #define RT_CULL_RAY(o, d) cull_ray_f(o, d)
 #define RT_CULL_TMAX(t) cull_tmax_f(t)
 #define RT_BOX_MAY_HIT(R, lo, hi, cr, tm) fbox_may_hit((R)->f##lo, (R)->f##hi, cr, tm)
 #else
 typedef CullRay CullR;
 typedef double CullT;
+#define RT_CULL_NEVER() CullRay{V3{__builtin_nan(""), __builtin_nan(""), __builtin_nan("")}, V3{0.0, 0.0, 0.0}}
 #define RT_CULL_RAY(o, d) cull_ray(o, d)
 #define RT_CULL_TMAX(t) cull_tmax(t)
 #define RT_BOX_MAY_HIT(R, lo, hi, cr, tm) box_may_hit((R)->lo, (R)->hi, cr, tm)
@@ -712,17 +714,47 @@ __device__ __forceinline__ void spec_for(F&& f) {
   }
 }
 // (RT_SPEC_FAMILY: a node's obj and skip are shared by every member of the family, spec.hip checks)
+// Tile masks (rt_tilemask.h; single-scene programs of reflection-only scenes): `mask` is wave-uniform,
+// bit o clear = no ray of this walk can have an accepted hit in object o's box.  A boxed object's node
+// is one scalar bit test; a group whose objects are all boxed is skipped when none of their bits is set
+// (both sets are compile-time constants).  Unbounded objects ignore the mask.
+#ifndef RT_TILE_MASKS
+#ifdef RT_SPEC_FAMILY
+#define RT_TILE_MASKS 0
+#else
+#define RT_TILE_MASKS 1
+#endif
+#endif
+template <bool SORD> constexpr uint32_t spec_boxed_bits(int b, int e) {     // the boxed objects of nodes [b, e)
+  uint32_t m = 0;
+  for (int i = b; i < e; ++i) {
+    const RtTrav& T = SORD ? rt_spec::STRAV[i] : rt_spec::TRAV[i];
+    if (T.obj >= 0 && T.obj < 32 && T.cull == RT_CULL_BOX) m |= 1u << T.obj;
+  }
+  return m;
+}
+template <bool SORD> constexpr bool spec_all_boxed(int b, int e) {          // no unbounded object in nodes [b, e)
+  for (int i = b; i < e; ++i) {
+    const RtTrav& T = SORD ? rt_spec::STRAV[i] : rt_spec::TRAV[i];
+    if (T.obj >= 32 || (T.obj >= 0 && T.cull == RT_CULL_NONE)) return false;
+  }
+  return true;
+}
 template <bool SORD, int I, int END, class G, class O>
-__device__ __forceinline__ void spec_walk(const DS& S, G& group, O& object) {
+__device__ __forceinline__ void spec_walk(const DS& S, G& group, O& object, uint32_t mask) {
   if constexpr (I < END) {
     constexpr RtTrav T = SORD ? rt_spec::STRAV[I] : rt_spec::TRAV[I];
     auto body = [&](cptr<RtTrav> TP) RT_INL {
       if constexpr (T.obj < 0) {
-        if (group(TP)) spec_walk<SORD, I + 1, T.skip>(S, group, object);
-        spec_walk<SORD, T.skip, END>(S, group, object);
+        constexpr bool GM = RT_TILE_MASKS && spec_all_boxed<SORD>(I + 1, T.skip);
+        constexpr uint32_t gbits = spec_boxed_bits<SORD>(I + 1, T.skip);
+        if (!GM || (mask & gbits) != 0u)
+          if (group(TP)) spec_walk<SORD, I + 1, T.skip>(S, group, object, mask);
+        spec_walk<SORD, T.skip, END>(S, group, object, mask);
       } else {
-        object(TP);
-        spec_walk<SORD, I + 1, END>(S, group, object);
+        constexpr bool OM = RT_TILE_MASKS && T.cull == RT_CULL_BOX && T.obj < 32;
+        if (!OM || ((mask >> (T.obj & 31)) & 1u) != 0u) object(TP);
+        spec_walk<SORD, I + 1, END>(S, group, object, mask);
       }
     };
     if constexpr (SORD) {
@@ -741,9 +773,10 @@ __device__ __forceinline__ void spec_walk(const DS& S, G& group, O& object) {
 // once no lane walks on, the generic walk ends (the spec walk's remaining branches are skipped by
 // the hardware, EXEC = 0).
 template <bool SORD, bool STOP = false, class G, class O>
-__device__ __forceinline__ void walk_trav(const DS& S, G&& group, O&& object, bool* done = nullptr) {
+__device__ __forceinline__ void walk_trav(const DS& S, G&& group, O&& object, bool* done = nullptr,
+                                          uint32_t mask = 0xffffffffu) {
 #ifdef RT_SPEC
-  spec_walk<SORD, 0, SORD ? rt_spec::N_STRAV : rt_spec::N_TRAV>(S, group, object);
+  spec_walk<SORD, 0, SORD ? rt_spec::N_STRAV : rt_spec::N_TRAV>(S, group, object, mask);
 #else
   // f32 culling: the compact nodes (RtTravC: two per scalar-cache line)
 #ifndef RT_TRAV_COMPACT
@@ -773,24 +806,36 @@ __device__ __forceinline__ void walk_trav(const DS& S, G&& group, O&& object, bo
 #endif
 }
 
+// The culling ray of a walk under a tile mask (spec_walk): a walk whose mask holds none of the scene's
+// boxed objects tests no object or group box, so it skips the ray's conversions and reciprocals (a
+// wave-uniform branch) and takes the ray that culls nothing (NaN slab times, as out of range): the
+// per-leaf boxes of unbounded objects, the only tests left, then always pass.
+template <bool SORD> __device__ __forceinline__ CullR walk_cull_ray(V3 o, V3 d, uint32_t mask) {
+#if defined(RT_SPEC) && RT_TILE_MASKS
+  constexpr uint32_t boxed = spec_boxed_bits<SORD>(0, SORD ? rt_spec::N_STRAV : rt_spec::N_TRAV);
+  if ((mask & boxed) == 0u) return RT_CULL_NEVER();
+#endif
+  return RT_CULL_RAY(o, d);
+}
+
 // Nearest hit over all objects in draw order: accept d if d > EPS && d < nearest
 // (raytracer.rs:141-150).  The acceptance test is pure, so it runs BEFORE the (pure) CSG
 // filter: candidates that cannot win never pay for the sibling is_inside tests.
 // SHARE: concentric sphere leaves reuse their ray terms (SphereShare); it keeps three doubles live
 // across the leaf loop, so only kernels with register headroom take it (see trace()).
 template <bool SHARE = false, bool OBB = !SHARE>
-RT_FN int nearest_hit(const DS& S, V3 ro, V3 rd, double* dist) {
+RT_FN int nearest_hit(const DS& S, V3 ro, V3 rd, double* dist, uint32_t mask = 0xffffffffu) {
   double best = INFINITY;
   int bobj = -1;
   SphereShare shr = {0.0, 0.0, 0.0};
-  const CullR cr = RT_CULL_RAY(ro, rd);
+  constexpr bool NORDER = RT_NEAREST_ORDER && OBB;
+  const CullR cr = walk_cull_ray<NORDER>(ro, rd, mask);
   const bool cf_ok = SHARE && RT_CONST_FILTER && const_filter_range(ro, rd);
   const bool fin = wave_finite(ro, rd);
   // NORDER (reflection-only kernels): the objects in S.strav's order, largest regions first, so an
   // early hit on a big object culls what lies behind it.  Exact: a candidate equal to the best
   // distance so far wins when its object comes earlier in DRAW order (o < bobj), which is the
   // reference's first-visited-wins rule (raytracer.rs:141-150) for any visiting order.
-  constexpr bool NORDER = RT_NEAREST_ORDER && OBB;
   auto group = [&](auto T) RT_INL { return node_may_hit(T, cr, RT_CULL_TMAX(best)); };
   auto object = [&](auto T) RT_INL {
     // the object's cull kind and box come from the node's copy (RtTrav): one scalar load for the
@@ -821,7 +866,7 @@ RT_FN int nearest_hit(const DS& S, V3 ro, V3 rd, double* dist) {
       }
     }
   };
-  walk_trav<NORDER>(S, group, object);
+  walk_trav<NORDER>(S, group, object, nullptr, mask);
   *dist = best;
   return bobj;
 }
@@ -834,14 +879,14 @@ RT_FN int nearest_hit(const DS& S, V3 ro, V3 rd, double* dist) {
 // order is free.  The early return ends the walk: `done` skips the rest of it (in the generic
 // walk a finished lane only rides along; the wave leaves once every lane is done).
 template <bool SHARE = false, bool OBB = !SHARE, bool SORDER = OBB>
-RT_FN double shadow_transparency(const DS& S, V3 p, V3 dir, double dist) {
+RT_FN double shadow_transparency(const DS& S, V3 p, V3 dir, double dist, uint32_t mask = 0xffffffffu) {
   RT_OPAQUE(p.x);
   RT_OPAQUE(p.y);
   RT_OPAQUE(p.z);
   double tr = 1.0;
   bool done = false;
   SphereShare shr = {0.0, 0.0, 0.0};
-  const CullR cr = RT_CULL_RAY(p, dir);
+  const CullR cr = walk_cull_ray<RT_SHADOW_ORDER && SORDER>(p, dir, mask);
   const bool cf_ok = SHARE && RT_CONST_FILTER && const_filter_range(p, dir);
   const bool fin = wave_finite(p, dir);
   const CullT tmax = RT_CULL_TMAX(dist);
@@ -874,7 +919,7 @@ RT_FN double shadow_transparency(const DS& S, V3 p, V3 dir, double dist) {
       }
     }
   };
-  walk_trav<RT_SHADOW_ORDER && SORDER, true>(S, group, object, &done);
+  walk_trav<RT_SHADOW_ORDER && SORDER, true>(S, group, object, &done, mask);
   return done ? 0.0 : tr;
 }
 
@@ -1185,7 +1230,25 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t m) {                 // s
 // frame never carries a pending reflection: frames are (A, w) as in the reflection-only kernels.
 template <bool REFR, class Rec = NoRec, int KL = 0, bool FC = false, int KLR = 0, bool CHAIN = false, int KP = 0>
 RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, lds_f64* lf = nullptr,
-                lds_f64* lp = nullptr) {
+                lds_f64* lp = nullptr, const uint32_t* tmask_ = nullptr) {
+  // Tile masks (rt_tilemask.h): the wave's RT_TILEMASK_WORDS words, read with scalar loads where a walk
+  // takes one.  Reflection-only kernels: every hit spawns at most one ray and a lane that spawns none
+  // leaves the loop, so iteration k traces the depth-k rays of the lanes still here.  The depth-0
+  // nearest hit takes `prim`; where every lane that hit something hit the mask plane (one ballot, kept
+  // in a scalar), light l's depth-0 shadow walk takes shadow[l] and the depth-1 nearest hit `refl`;
+  // every other walk takes all ones.  One walk either way: the mask is an operand, not a second copy.
+#if defined(RT_SPEC) && RT_TILE_MASKS
+  constexpr bool MASKS = !REFR && same_type<Rec, NoRec>::value;
+  constexpr int mask_plane = rt_spec::MASK_PLANE;
+#else
+  constexpr bool MASKS = false;
+  constexpr int mask_plane = -1;
+#endif
+  const cptr<uint32_t> tmask = as_const(tmask_);
+  auto mask_word = [&](int k) -> uint32_t {
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)tmask[k]);
+  };
+  [[maybe_unused]] bool plane_tile = false;   // depth 0: every hit of the wave is on the mask plane
   double fA[RT_MAX_DEPTH_CAP][3];     // parent colour already intensified by (1 - w)
   double fW[RT_MAX_DEPTH_CAP];        // child weight w (transparency or reflectivity)
   constexpr bool POOL = KP > 0 && !(REFR && !CHAIN) && same_type<Rec, NoRec>::value;
@@ -1277,7 +1340,25 @@ RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, ld
     [[maybe_unused]] double push_w = 0.0;
     double t_hit;
     int oi;
-    oi = nearest_hit<SHARE, OBB>(S, ro, rd, &t_hit);
+    uint32_t nmask = 0xffffffffu;
+    if constexpr (MASKS) {
+      // `iter` and `plane_tile` are the same in every lane still here, but both are carried round a loop
+      // that lanes leave one by one, so the compiler takes them for per-lane values: the choice is made on
+      // their first active lane's copies, which keeps the mask (and every test on it) scalar.
+      const int it = __builtin_amdgcn_readfirstlane(iter);
+      const bool pt = __builtin_amdgcn_readfirstlane((int)plane_tile) != 0;
+      if (tmask_ && it == 0) nmask = mask_word(0);
+      else if (pt && it == 1) nmask = mask_word(5);
+      nmask = (uint32_t)__builtin_amdgcn_readfirstlane((int)nmask);
+    }
+    oi = nearest_hit<SHARE, OBB>(S, ro, rd, &t_hit, nmask);
+    // depth 0: is every hit of the wave on the mask plane?  Voted here, by every lane of the iteration
+    // (a lane that missed takes no part in what follows), not inside the branch of the lanes that hit.
+    // (`refl` at iteration 1 rests on this flag alone: it is only ever written here, at iteration 0, which
+    // no lane re-enters -- the bounce loop never restarts a pixel.  A change that lets a lane take a second
+    // primary ray inside this loop must clear plane_tile with it.)
+    if constexpr (MASKS)
+      if (iter == 0) plane_tile = tmask_ && mask_plane >= 0 && __ballot(oi >= 0 && oi != mask_plane) == 0;
     const V3 p = add(ro, scale(rd, t_hit));                               // :162
     if constexpr (RECORD) slot = rec->begin(depth, ray_type, ro, rd, t_hit, oi, p);
     V3 nrm = {0.0, 0.0, 0.0};
@@ -1300,7 +1381,10 @@ RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, ld
         len_inv(lv, &ll, &ill);
         const V3 sdir = scale(lv, ill);                                    // normalized(lv)
         double t;                                                          // :176-197
-        t = shadow_transparency<SHARE, OBB>(S, p, sdir, ll);
+        uint32_t smask = 0xffffffffu;
+        if constexpr (MASKS)
+          if (__builtin_amdgcn_readfirstlane((int)(plane_tile && iter == 0)) != 0 && k < 4) smask = mask_word(1 + k);
+        t = shadow_transparency<SHARE, OBB>(S, p, sdir, ll, smask);
         if (!have_shading) {
           shade_inputs(S, oi, p, &nrm, &c, &transp, &refl, &nlen);
           L = cmul<FC>(c, in_range<FC>(0.6, 0.6, 0.6));                      // ambient (:172)
@@ -1750,7 +1834,7 @@ template <int MODE, bool F64, bool CAL, bool FC, int KL_ = -1, int KP_ = -1, boo
 __device__ __forceinline__ void rows_entry(const RtDevScene& S, unsigned entry, int y_first, int band_rows, int band_pitch,
                                            int n_rows, int max_depth, uint8_t* __restrict__ out, size_t stride,
                                            const int32_t* __restrict__ order, uint32_t* __restrict__ cost, int rgb,
-                                           lds_f64* frames) {
+                                           lds_f64* frames, const uint32_t* __restrict__ masks = nullptr) {
   constexpr bool REFR = MODE != RT_MODE_REFL, CHAIN = MODE == RT_MODE_CHAIN;
   constexpr int KLR = PRIM ? 0 : MODE == RT_MODE_TREE ? RT_LDS_RFRAMES : 0;
   constexpr int KP = PRIM ? 0 : rows_pool_slots<MODE, KL_, KP_>();
@@ -1767,8 +1851,11 @@ __device__ __forceinline__ void rows_entry(const RtDevScene& S, unsigned entry, 
   if (y >= S.height) return;
   V3 ro, rd;
   camera_ray_px(S, x, y, &ro, &rd);                                         // get_pixel(x as f64, y as f64)
+  // the tile's mask words (null: all ones); the tile index is the same in every lane
+  const uint32_t* tmask =
+      masks ? masks + (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)tile) * RT_TILEMASK_WORDS : nullptr;
   const Col c = trace<REFR, NoRec, KL, FC, KLR, CHAIN, KP>(make_ds(S), ro, rd, max_depth, nullptr, PRIM ? nullptr : frames + lane,
-                                                         frames);
+                                                         frames, tmask);
   store_pixel<F64, PRIM>(out + (size_t)r * stride, x, c, rgb);
   if constexpr (CAL)
     if (threadIdx.x == 0) cost[tile] = (uint32_t)(wall_clock64() - t_start);   // vector store
@@ -1777,9 +1864,9 @@ template <int MODE, bool F64, bool CAL, bool FC, int KL_ = -1, int KP_ = -1, boo
 __device__ __forceinline__ void rows_body(const RtDevScene& S, int y_first, int band_rows, int band_pitch, int n_rows,
                                           int max_depth, uint8_t* __restrict__ out, size_t stride,
                                           const int32_t* __restrict__ order, uint32_t* __restrict__ cost, int rgb,
-                                          lds_f64* frames) {
+                                          lds_f64* frames, const uint32_t* __restrict__ masks = nullptr) {
   rows_entry<MODE, F64, CAL, FC, KL_, KP_, PRIM>(S, blockIdx.x, y_first, band_rows, band_pitch, n_rows, max_depth, out,
-                                                 stride, order, cost, rgb, frames);
+                                                 stride, order, cost, rgb, frames, masks);
 }
 template <int MODE, int KL_ = -1, int KP_ = -1>
 constexpr int rows_lds_doubles() {

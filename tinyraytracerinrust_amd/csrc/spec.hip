@@ -260,6 +260,10 @@ static std::string spec_source(const FlatScene& f, const SpecFamily* fam) {
            "constexpr int N_OBJECTS = %d, N_LIGHTS = %d, N_TRAV = %d, N_STRAV = %d, SHADOW_EARLY_OUT = %d;\n",
            (int)f.objects.size(), (int)f.lights.size(), (int)f.trav.size(), (int)f.strav.size(), f.shadow_early_out);
   s += buf;
+  // the tile masks' plane (rt_tilemask.h): the object the mask tables' shadow and refl words were built for
+  // (a family program takes no masks: its members' planes and boxes differ)
+  snprintf(buf, sizeof buf, "constexpr int MASK_PLANE = %d;\n", fam ? -1 : tilemask_plane(f));
+  s += buf;
   emit_table(s, "RtObject", "OBJECTS", f.objects, fam ? &fam->v_obj : nullptr);
   emit_table(s, "RtTrav", "TRAV", f.trav, fam ? &fam->v_trav : nullptr);
   emit_table(s, "RtTrav", "STRAV", f.strav, fam ? &fam->v_strav : nullptr);
@@ -277,8 +281,10 @@ static std::string spec_source(const FlatScene& f, const SpecFamily* fam) {
 static std::string spec_kernel(int kind, int mode, bool fc, int f64, int cal) {
   static const char* args =
       "(RtDevScene S, int y_first, int band_rows, int band_pitch, int n_rows, int max_depth, uint8_t* __restrict__ out, "
-      "size_t stride, const int32_t* __restrict__ order, uint32_t* __restrict__ cost, int rgb)";
-  char buf[1024], waves[64];
+      "size_t stride, const int32_t* __restrict__ order, uint32_t* __restrict__ cost, int rgb";
+  // the megakernel and the primary-ray kernel also take the launch geometry's tile-mask table (null: all ones)
+  const std::string args_m = std::string(args) + ", const uint32_t* __restrict__ masks)", args_d = std::string(args) + ")";
+  char buf[1280], waves[64];
   // The specialised megakernel runs 4 waves/SIMD (128 VGPRs): its unrolled walks keep more values
   // live than the generic loop, and at the generic reflection kernel's 5 waves (96 VGPRs) it spilled
   // 62 VGPRs; 4 waves measured 4.9 % faster on 4K globes (0.3499 vs 0.3679 ms,
@@ -314,23 +320,23 @@ static std::string spec_kernel(int kind, int mode, bool fc, int f64, int cal) {
              "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(%d))) "
              "void rt_spec_prim_%d%d%s {\n"
              "  rows_body<%d, %s, %s, %s, 0, 0, true>(S, y_first, band_rows, band_pitch, n_rows, 0, out, stride, order, "
-             "cost, rgb, nullptr);\n}\n",
-             RT_SPEC_WAVES_PRIM, f64, cal, args, mode, f64 ? "true" : "false", cal ? "true" : "false", fc ? "true" : "false");
-  else if (kind == 0)
+             "cost, rgb, nullptr, masks);\n}\n",
+             RT_SPEC_WAVES_PRIM, f64, cal, args_m.c_str(), mode, f64 ? "true" : "false", cal ? "true" : "false", fc ? "true" : "false");
+  else if (kind == 0 || kind == 3)    // 3: the megakernel of the mask-free program (spec_programs), a null table
     snprintf(buf, sizeof buf,
              "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(%s))) "
              "void rt_spec_rows_%d%d%s {\n  __shared__ double s_frames[rows_lds_doubles<%d, %d, %d>()];\n"
              "  rows_body<%d, %s, %s, %s, %d, %d>(S, y_first, band_rows, band_pitch, n_rows, max_depth, out, stride, order, "
-             "cost, rgb, (lds_f64*)s_frames);\n}\n",
-             waves, f64, cal, args, mode, kl, kp, mode, f64 ? "true" : "false", cal ? "true" : "false", fc ? "true" : "false",
-             kl, kp);
+             "cost, rgb, (lds_f64*)s_frames, %s);\n}\n",
+             waves, f64, cal, args_m.c_str(), mode, kl, kp, mode, f64 ? "true" : "false", cal ? "true" : "false", fc ? "true" : "false",
+             kl, kp, kind == 3 ? "nullptr" : "masks");
   else
     snprintf(buf, sizeof buf,
              "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RT_WAVES_PER_EU_DEFERRED))) "
              "void rt_spec_def_%d%d%s {\n  __shared__ ShadowWin win;\n"
              "  deferred_body<%s, %s, %s, %s>(S, y_first, band_rows, band_pitch, n_rows, max_depth, out, stride, order, "
              "cost, rgb, &win);\n}\n",
-             f64, cal, args, f64 ? "true" : "false", cal ? "true" : "false", fc ? "true" : "false",
+             f64, cal, args_d.c_str(), f64 ? "true" : "false", cal ? "true" : "false", fc ? "true" : "false",
              mode == RT_MODE_REFL ? "false" : "true");
   return buf;
 }
@@ -342,7 +348,7 @@ static std::string spec_kernel(int kind, int mode, bool fc, int f64, int cal) {
 // Each kernel is its own program (prelude + one kernel): the programs compile in parallel, and the
 // inliner sees one kernel per module.
 struct SpecKernel { int kind, f64, cal; };
-static std::vector<SpecKernel> spec_kernels(const rt_ctx* c) {
+static std::vector<SpecKernel> spec_kernels(const rt_ctx* c, bool with_nm) {
   std::vector<SpecKernel> v;
   const int n = c->spec_on >= 2 ? 2 : 1;
   for (int kind = 0; kind < 3; ++kind) {
@@ -350,14 +356,26 @@ static std::vector<SpecKernel> spec_kernels(const rt_ctx* c) {
     for (int f64 = 0; f64 < n; ++f64)
       for (int cal = 0; cal < n; ++cal) v.push_back({kind, f64, cal});
   }
+  // The masked walks cost a few percent whether a mask rules anything out or not (DESIGN.md "Tile masks"),
+  // so a program whose megakernel reads masks also holds the megakernel without them -- the same kernel name
+  // in a module of its own -- and launch_bands takes it for the launches that pass no table.  with_nm: a
+  // CONTEXT's programs (spec_prepare / spec_poll).  A scene's programs as rt_scene_precompile, _spec_report and
+  // _spec_program name them are the level's kernels, one each; the mask-free megakernel is requested (in the
+  // background, like the others) by the context that uploads the scene.
+  if (with_nm && c->spec_mode == RT_MODE_REFL && !c->spec_family)
+    for (int f64 = 0; f64 < n; ++f64)
+      for (int cal = 0; cal < n; ++cal) v.push_back({3, f64, cal});
   return v;
 }
 static const char* spec_kernel_name(int kind) {
-  return kind == 2 ? "rt_spec_prim_%d%d" : kind == 1 ? "rt_spec_def_%d%d" : "rt_spec_rows_%d%d";
+  return kind == 2 ? "rt_spec_prim_%d%d" : kind == 1 ? "rt_spec_def_%d%d" : "rt_spec_rows_%d%d";   // kinds 0 and 3
 }
-static std::vector<std::string> spec_programs(const rt_ctx* c) {
+static std::vector<std::string> spec_programs(const rt_ctx* c, bool with_nm = false) {
   std::vector<std::string> v;
-  for (const SpecKernel& k : spec_kernels(c)) v.push_back(c->spec_src + spec_kernel(k.kind, c->spec_mode, c->spec_fc, k.f64, k.cal));
+  // kind 3 (the mask-free megakernel) is a program compiled with RT_TILE_MASKS 0: the device code without the
+  // mask operand, not merely a null table
+  for (const SpecKernel& k : spec_kernels(c, with_nm))
+    v.push_back((k.kind == 3 ? "#define RT_TILE_MASKS 0\n" : "") + c->spec_src + spec_kernel(k.kind, c->spec_mode, c->spec_fc, k.f64, k.cal));
   return v;
 }
 
@@ -808,6 +826,7 @@ void spec_drop(rt_ctx* c) {
   memset(c->spec_mods, 0, sizeof c->spec_mods);
   c->spec_mod = nullptr;
   memset(c->spec_rows, 0, sizeof c->spec_rows);
+  memset(c->spec_rows_nm, 0, sizeof c->spec_rows_nm);
   memset(c->spec_def, 0, sizeof c->spec_def);
   memset(c->spec_prim, 0, sizeof c->spec_prim);
   c->spec_jobs.clear();                                   // drops this context's interest
@@ -821,7 +840,7 @@ void spec_prepare(rt_ctx* c, bool retry) {
   if (!c->spec_on || !c->spec_flat || !c->spec_fits) return;
   spec_text(*c->spec_flat, c);
   bool all_done = true;
-  for (const std::string& t : spec_programs(c)) {
+  for (const std::string& t : spec_programs(c, true)) {
     bool done = false;
     c->spec_jobs.push_back(spec_request(t, retry, &done));
     all_done = all_done && done;
@@ -841,7 +860,7 @@ int spec_poll(rt_ctx* c) {
       return RT_OK;
     }
   char name[32];
-  const std::vector<SpecKernel> ks = spec_kernels(c);
+  const std::vector<SpecKernel> ks = spec_kernels(c, true);
   double ms = 0.0;
   bool disk = false;
   std::string res;
@@ -851,7 +870,8 @@ int spec_poll(rt_ctx* c) {
     hipError_t e = hipModuleLoadData(&c->spec_mods[i], code.code.data());
     if (e == hipSuccess) {
       snprintf(name, sizeof name, spec_kernel_name(k.kind), k.f64, k.cal);
-      hipFunction_t* fn = k.kind == 2 ? &c->spec_prim[k.f64][k.cal] : k.kind ? &c->spec_def[k.f64][k.cal] : &c->spec_rows[k.f64][k.cal];
+      hipFunction_t* fn = k.kind == 3 ? &c->spec_rows_nm[k.f64][k.cal] : k.kind == 2 ? &c->spec_prim[k.f64][k.cal]
+                          : k.kind ? &c->spec_def[k.f64][k.cal] : &c->spec_rows[k.f64][k.cal];
       e = hipModuleGetFunction(fn, c->spec_mods[i], name);
     }
     if (e != hipSuccess) {
@@ -984,7 +1004,7 @@ extern "C" int rt_scene_spec_program(const rt_scene* s, char* buf, size_t cap, s
   tmp.spec_on = 2;
   rt::spec_text(f, &tmp);
   std::string text = tmp.spec_src;
-  for (const rt::SpecKernel& k : rt::spec_kernels(&tmp)) text += rt::spec_kernel(k.kind, tmp.spec_mode, tmp.spec_fc, k.f64, k.cal);
+  for (const rt::SpecKernel& k : rt::spec_kernels(&tmp, false)) text += rt::spec_kernel(k.kind, tmp.spec_mode, tmp.spec_fc, k.f64, k.cal);
   *len = text.size();
   if (cap > 0) {
     const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;

@@ -175,6 +175,20 @@ class Scene:
         check(lib().rt_scene_spec_program(self.h, buf, n.value + 1, ctypes.byref(n)))
         return buf.value.decode()
 
+    def tile_masks(self, y_first: int = 0, band_rows: Optional[int] = None, band_pitch: Optional[int] = None,
+                   n_bands: int = 1):
+        """rt_scene_tile_masks: the per-tile object masks of a band launch (default: the whole frame),
+        evaluated on the host -> (uint32 array [tiles, 6]: prim, shadow[0..3], refl; info dict)."""
+        band_rows = self.height - y_first if band_rows is None else band_rows
+        band_pitch = band_rows if band_pitch is None else band_pitch
+        tiles = ((self.width + 7) // 8) * ((band_rows * n_bands + 7) // 8)
+        words = np.zeros((tiles, _lib.RT_TILEMASK_WORDS), dtype=np.uint32)
+        info = (ctypes.c_int32 * 4)()
+        check(lib().rt_scene_tile_masks(self.h, y_first, band_rows, band_pitch, n_bands,
+                                        ctypes.c_void_p(words.ctypes.data), words.size, info))
+        assert info[0] == tiles, (info[0], tiles)
+        return words, {"tiles": info[0], "plane": info[1], "boxed": info[2] & 0xffffffff, "valid": bool(info[3])}
+
     def precompile(self) -> float:
         """rt_scene_precompile: compile the specialised program into the process cache (no device);
         returns the hipRTC milliseconds (0 when cached)."""
@@ -403,6 +417,27 @@ class Renderer:
         check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_SPECIALIZE, int(level)))
         if wait and level:
             self.spec_wait()
+
+    def set_tile_masks(self, mode) -> None:
+        """rt_ctx_set_option(RT_OPT_TILE_MASKS): per-tile object masks for the specialised reflection-only
+        kernels (same pixels): 0 / False never, 1 (the default) where the geometry's calibration found them
+        to pay, 2 / True for every launch that can take them."""
+        v = (2 if mode else 0) if isinstance(mode, bool) else int(mode)
+        check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_TILE_MASKS, v))
+
+    def tile_masks(self, y_first: int = 0, band_rows: Optional[int] = None, band_pitch: Optional[int] = None,
+                   n_bands: int = 1) -> np.ndarray:
+        """rt_ctx_tile_masks: the uploaded scene's mask table of a band launch (default: the whole frame)
+        as the device computed it, uint32 [tiles, 6]."""
+        band_rows = self.height - y_first if band_rows is None else band_rows
+        band_pitch = band_rows if band_pitch is None else band_pitch
+        tiles = ((self.width + 7) // 8) * ((band_rows * n_bands + 7) // 8)
+        words = np.zeros((tiles, _lib.RT_TILEMASK_WORDS), dtype=np.uint32)
+        n = ctypes.c_uint32()
+        check(lib().rt_ctx_tile_masks(self.h, y_first, band_rows, band_pitch, n_bands,
+                                      ctypes.c_void_p(words.ctypes.data), words.size, ctypes.byref(n)))
+        assert n.value == tiles, (n.value, tiles)
+        return words
 
     def spec_wait(self, timeout_ms: int = -1) -> bool:
         """rt_ctx_spec_wait: block until the scene-specialised program is loaded (True), or until

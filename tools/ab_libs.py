@@ -2,7 +2,8 @@
 (bench.py's N = 1 arrangement), each library through its own ctypes handle, context and upload, with
 the specialised kernels loaded (RT_OPT_SPECIALIZE 1, rt_ctx_spec_wait) unless --generic.  Prints the
 ms per frame (one event pair around --frames launches) per library, median over --rounds.
-usage: python tools/ab_libs.py LIB [LIB ...] [--config sphere1080d0|globes1080d5|globes4k] [--generic]"""
+usage: python tools/ab_libs.py LIB [LIB ...] [--config sphere1080d0|globes1080d5|globes4k|spin1080|fractal1080] [--generic]
+       [--masks=-1,1,0]   per library: RT_OPT_TILE_MASKS (-1: leave it, for libraries without the option)"""
 import argparse
 import ctypes
 import os
@@ -13,7 +14,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 S = os.path.join(ROOT, "tests", "golden", "scenes")
 CONFIGS = {"sphere1080d0": (None, 1920, 1080, 0), "globes1080d5": ("globes", 1920, 1080, 5),
-           "globes4k": ("globes", 3840, 2160, 10)}
+           "globes4k": ("globes", 3840, 2160, 10),
+           # refraction chains (its own chain-mode program) and a scene too large to specialise (generic kernels)
+           "spin1080": ("spinning_globes", 1920, 1080, 10), "fractal1080": ("fractal", 1920, 1080, 10)}
 
 
 def main():
@@ -26,19 +29,23 @@ def main():
     ap.add_argument("--no-check", action="store_true", help="ablation libraries: do not require equal frames")
     ap.add_argument("--levels", default="", help="per library (in order): its RT_OPT_SPECIALIZE level, e.g. 1,2 "
                                                    "(a library path may repeat); default 1 (0 with --generic)")
+    ap.add_argument("--masks", default="", help="per library (in order): RT_OPT_TILE_MASKS, -1 = leave the default")
     a = ap.parse_args()
     import torch
     scene, W, H, depth = CONFIGS[a.config]
     text = (open(os.path.join(S, scene + ".scene")).read() if scene else "draw(sphere(<0, 0, 0>, 30, red))").encode()
     ctxs, outs = [], []
     levels = [int(v) for v in a.levels.split(",")] if a.levels else [0 if a.generic else 1] * len(a.libs)
-    for path, level in zip(a.libs, levels):
+    masks = [int(v) for v in a.masks.split(",")] if a.masks else [-1] * len(a.libs)
+    for path, level, mask in zip(a.libs, levels, masks):
         L = ctypes.CDLL(os.path.abspath(path), mode=os.RTLD_LOCAL)
         L.rt_ctx_spec_wait.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         sc, cx = ctypes.c_void_p(), ctypes.c_void_p()
         assert L.rt_scene_compile(text, S.encode(), ctypes.c_double(0.0), W, H, ctypes.byref(sc)) == 0
         assert L.rt_ctx_create(0, ctypes.byref(cx)) == 0
         assert L.rt_ctx_set_option(cx, 6, level) == 0
+        if mask >= 0:
+            assert L.rt_ctx_set_option(cx, 8, mask) == 0               # RT_OPT_TILE_MASKS
         assert L.rt_ctx_upload(cx, sc) == 0
         assert L.rt_ctx_spec_wait(cx, -1) == 0
         assert L.rt_ctx_set_option(cx, 1, 0) == 0                  # RT_OPT_TIMING off, as bench.py
@@ -79,9 +86,10 @@ def main():
         if not a.no_check and not torch.equal(outs[i], outs[0]):
             raise SystemExit(f"{a.libs[i]}: frame differs from {a.libs[0]}'s")
     print(f"{a.config} ({'generic' if a.generic else 'specialised'}), {n} frames per measurement, ms per frame, median of {a.rounds}:")
-    for path, level, v in zip(a.libs, levels, res):
+    for path, level, mask, v in zip(a.libs, levels, masks, res):
         w = sorted(v)
-        print(f"  {w[len(w) // 2]:.4f}  ({' '.join(f'{x:.4f}' for x in v)})  {path} (RT_OPT_SPECIALIZE {level})", flush=True)
+        print(f"  {w[len(w) // 2]:.4f}  ({' '.join(f'{x:.4f}' for x in v)})  {path} (RT_OPT_SPECIALIZE {level}"
+              f"{'' if mask < 0 else f', RT_OPT_TILE_MASKS {mask}'})", flush=True)
 
 
 if __name__ == "__main__":
