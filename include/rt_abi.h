@@ -118,6 +118,25 @@ int rt_scene_add_light(rt_scene* scene, const double point[3], const double colo
  * world space (raytracer.rs:289-299 applies the transform; the DSL applies it once before). */
 int rt_scene_set_camera(rt_scene* scene, const double center[3]);
 int rt_scene_set_max_depth(rt_scene* scene, int32_t max_depth);                  /* raytracer.rs:65 */
+/* The scene's Camera (camera.rs:5-9): PerspectiveCamera (:17-79, the default), StereoscopicCamera
+ * (:82-141: two eyes side by side, each W / 2 wide; columns x >= W / 2 show the LEFT eye at x - W / 2, the
+ * others the right eye, :124-128) or AnaglyphCamera (:143-205: red from the left eye, green and blue from
+ * the right, alpha 1, :186-195).  The eyes are PerspectiveCameras looking at the origin from
+ * center -+ right * (eye_distance / 2) (:108-112, :169-173), `right` being rt_scene_get_camera's.  The kind
+ * is a property of the scene: it survives rt_scene_set_camera, the eyes being derived from the centre when
+ * the scene is flattened.  rt_scene_compile makes perspective scenes (the DSL has no syntax for the others,
+ * and the reference's GUI constructs neither).  RT_ERR_INVALID: an unknown kind, a non-finite eye distance,
+ * stereoscopic on a scene less than 2 pixels wide.
+ * Every get_pixel path follows the kind: rt_render_rows / _f64 / _row_bands / _row_bands_rgb8,
+ * rt_render_points_f64, rt_trace_pixel_f64.  rt_render_ortho does not use the camera.  Out of scope for
+ * two-eye scenes (RT_ERR_UNSUPPORTED): rt_antialias, rt_record_rays, rt_ctx_tile_masks, rt_scene_tile_masks. */
+typedef enum rt_camera_kind { RT_CAMERA_PERSPECTIVE = 0, RT_CAMERA_STEREOSCOPIC = 1, RT_CAMERA_ANAGLYPH = 2 } rt_camera_kind;
+int rt_scene_set_camera_kind(rt_scene* scene, int32_t kind, double eye_distance);
+int rt_scene_get_camera_kind(const rt_scene* scene, int32_t* kind, double* eye_distance);
+/* One eye's PerspectiveCamera as StereoscopicCamera::new / AnaglyphCamera::new build it (camera.rs:108-112,
+ * :169-173): eye 0 = left, 1 = right; out as rt_scene_get_camera (the stereoscopic eyes' aspect ratio is
+ * (W / 2) / H).  RT_ERR_INVALID: an eye index outside 0..1, or a perspective scene. */
+int rt_scene_get_camera_eye(const rt_scene* scene, int32_t eye, double out[13]);
 /* Whole-scene front end: restates load_scene (scene_loader.rs:24-47) on a fresh
  * new_default()+add_test_objects() RayTracer (debug_window.rs:53-62), with the global `time`
  * set (time = frame / 300 in the reference GUI).  Texture paths resolve against asset_dir
@@ -305,6 +324,9 @@ int rt_ctx_synchronize(rt_ctx* ctx);
  * (costliest tile <= the work per wave slot; launches without a measured order take none); 2 every launch
  * that can; 0 none (the mask-free kernels: the walks of a library without masks).  Same pixels.
  * rt_ctx_kernel_info says whether the last launch took masks.
+ * Two-eye scenes (rt_scene_set_camera_kind) always take the view megakernels (k_stereo.hip: one launch over
+ * the tiles of both eyes, mask-free walks): RT_KERNEL_DEFERRED, RT_KERNEL_WAVEFRONT and RT_OPT_TILE_MASKS have
+ * no effect on them; RT_OPT_TILE_ORDER and RT_OPT_SPECIALIZE apply (rt_ctx_kernel_info says which kernel ran).
  * Option 7 is retired (round 4's tail kernel, measured slower than the launch it shortened). */
 typedef enum rt_option {
   RT_OPT_KERNEL = 0, RT_OPT_TIMING = 1, RT_OPT_TILE_ORDER = 2, RT_OPT_FAST_CLAMP = 3, RT_OPT_WAVEFRONT_CAP = 4,

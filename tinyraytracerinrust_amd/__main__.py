@@ -2,6 +2,7 @@
 
     python -m tinyraytracerinrust_amd render SCENE [--size WxH] [--time T | --frame F]
                                           [--depth D] [--gpus N] [-o out.png]
+                                          [--camera {perspective,stereoscopic,anaglyph} --eye-distance D]
 
 Replaces the reference's entry point and its GUI load path for this purpose: ``main()`` only
 starts the GTK application (src/main.rs:7-9), which builds a RayTracer per frame with
@@ -42,8 +43,14 @@ def _parse(argv):
     r.add_argument("--band", type=int, default=8)
     r.add_argument("--assets", default=None, help="directory textures resolve against (default: the scene's)")
     r.add_argument("--channels", type=int, default=3, choices=[3, 4], help="PNG channels (RGB or RGBA)")
+    r.add_argument("--camera", default="perspective", choices=["perspective", "stereoscopic", "anaglyph"],
+                   help="the scene's Camera (camera.rs): stereoscopic = two eyes side by side, anaglyph = red/cyan")
+    r.add_argument("--eye-distance", type=float, default=None,
+                   help="distance between the two eyes, scene units (required for stereoscopic / anaglyph)")
     r.add_argument("-o", "--output", default="out.png")
     a = ap.parse_args(argv)
+    if a.camera != "perspective" and a.eye_distance is None:
+        ap.error(f"--camera {a.camera} needs --eye-distance (the reference constructs neither camera: no default)")
     try:
         w, h = a.size.lower().split("x")
         a.width, a.height = int(w), int(h)
@@ -98,6 +105,8 @@ def render(a) -> dict:
     if scene.status:
         print(f"scene parse error (rendering the default scene, as the reference does): {scene.error}",
               file=sys.stderr)
+    if a.camera != "perspective":
+        scene.set_camera_kind(a.camera, a.eye_distance)
     times["compile_ms"] = (time.perf_counter() - t0) * 1e3
     t0 = time.perf_counter()
     r = Renderer(local)

@@ -30,6 +30,9 @@ RT_OPT_SPECIALIZE = 6
 RT_OPT_TILE_MASKS = 8
 RT_TILEMASK_WORDS = 6     # per tile: prim, shadow[0..3], refl
 RT_KERNEL_AUTO, RT_KERNEL_MEGA, RT_KERNEL_DEFERRED, RT_KERNEL_WAVEFRONT = 0, 1, 2, 3
+RT_CAMERA_PERSPECTIVE, RT_CAMERA_STEREOSCOPIC, RT_CAMERA_ANAGLYPH = 0, 1, 2
+CAMERA_KINDS = {"perspective": RT_CAMERA_PERSPECTIVE, "stereoscopic": RT_CAMERA_STEREOSCOPIC,
+                "anaglyph": RT_CAMERA_ANAGLYPH}
 
 
 class RtError(RuntimeError):
@@ -76,6 +79,9 @@ SIGNATURES = {
     "rt_scene_add_light": (_I, [_P, _D3, _D3, ctypes.c_double]),
     "rt_scene_set_camera": (_I, [_P, _D3]),
     "rt_scene_set_max_depth": (_I, [_P, ctypes.c_int32]),
+    "rt_scene_set_camera_kind": (_I, [_P, ctypes.c_int32, ctypes.c_double]),
+    "rt_scene_get_camera_kind": (_I, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]),
+    "rt_scene_get_camera_eye": (_I, [_P, ctypes.c_int32, _D3]),
     "rt_scene_compile": (_I, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double, _U32, _U32,
                               ctypes.POINTER(_P)]),
     "rt_scene_traversal": (_I, [_P, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,

@@ -183,6 +183,7 @@ int rt_ctx_tile_masks(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t 
                       uint32_t* words, size_t cap_words, uint32_t* n_tiles_out) {
   if (!c || !n_tiles_out || (cap_words > 0 && !words)) return fail(RT_ERR_INVALID, "null argument");
   if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
+  if (c->views.kind) return fail(RT_ERR_UNSUPPORTED, "rt_ctx_tile_masks is not built for a two-eye scene (stereoscopic / anaglyph camera)");
   int n_rows = 0;
   size_t n_tiles = 0;
   RT_TRY(mask_geometry(c->dev.width, c->dev.height, y_first, band_rows, band_pitch, n_bands, &n_rows, &n_tiles));
@@ -204,6 +205,8 @@ int rt_ctx_tile_masks(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t 
 int rt_scene_tile_masks(const rt_scene* s, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
                         uint32_t* words, size_t cap_words, int32_t info[4]) {
   if (!s || !info || (cap_words > 0 && !words)) return fail(RT_ERR_INVALID, "null argument");
+  if (s->cam_kind != RT_CAMERA_PERSPECTIVE)
+    return fail(RT_ERR_UNSUPPORTED, "rt_scene_tile_masks is not built for a two-eye scene (stereoscopic / anaglyph camera)");
   rt::FlatScene f;
   RT_TRY(rt::flatten(*s, &f));
   int n_rows = 0;

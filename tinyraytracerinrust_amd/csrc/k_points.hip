@@ -26,6 +26,29 @@ __global__ __launch_bounds__(256) void render_points_kernel(RtDevScene S, const 
   out[4 * i] = c.r; out[4 * i + 1] = c.g; out[4 * i + 2] = c.b; out[4 * i + 3] = 1.0;
 }
 
+// The same for a two-eye scene (rt_blob.h RtViews).  Stereoscopic (camera.rs:124-131): a sample at
+// x >= W / 2 (as f64) is the LEFT eye's at x - W / 2 (view 1), any other the right eye's at x (view 0).
+// Anaglyph (:186-195): both eyes' rays at (x, y), view 0 (left) giving r, view 1 (right) g and b.
+template <bool REFR>
+__global__ __launch_bounds__(256) void render_points_views_kernel(RtDevScene S, RtViews VW, const double* __restrict__ xy,
+                                                                  size_t n, int max_depth, double* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool anaglyph = VW.kind == RT_CAMERA_ANAGLYPH;
+  const double w = (double)VW.stereo_w, y = xy[2 * i + 1];
+  double x = xy[2 * i];
+  int eye = 0;
+  if (!anaglyph && x >= w) { x = x - w; eye = 1; }
+#pragma unroll 1
+  for (int k = 0; k < (anaglyph ? 2 : 1); ++k) {
+    V3 ro, rd;
+    camera_ray(VW.v[anaglyph ? k : eye].cam, x, y, &ro, &rd);
+    const Col c = trace<REFR>(make_ds(S), ro, rd, max_depth);
+    if (!anaglyph || k == 0) out[4 * i] = c.r;
+    if (!anaglyph || k == 1) { out[4 * i + 1] = c.g; out[4 * i + 2] = c.b; out[4 * i + 3] = 1.0; }
+  }
+}
+
 }  // namespace
 
 using namespace rt;
@@ -75,7 +98,11 @@ int rt_render_points_f64(rt_ctx* c, const double* xy, size_t n, int32_t max_dept
   }
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
   if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
-  if (c->dev.any_transparent) hipLaunchKernelGGL((render_points_kernel<true>), grid, block, 0, st, c->dev, in, n, max_depth, target);
+  if (c->views.kind && c->dev.any_transparent)
+    hipLaunchKernelGGL((render_points_views_kernel<true>), grid, block, 0, st, c->dev, c->views, in, n, max_depth, target);
+  else if (c->views.kind)
+    hipLaunchKernelGGL((render_points_views_kernel<false>), grid, block, 0, st, c->dev, c->views, in, n, max_depth, target);
+  else if (c->dev.any_transparent) hipLaunchKernelGGL((render_points_kernel<true>), grid, block, 0, st, c->dev, in, n, max_depth, target);
   else hipLaunchKernelGGL((render_points_kernel<false>), grid, block, 0, st, c->dev, in, n, max_depth, target);
   RT_HIP(hipGetLastError());
   if (c->timing) RT_HIP(hipEventRecord(c->ev1, st));

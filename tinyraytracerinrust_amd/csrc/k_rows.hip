@@ -131,6 +131,10 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   const int a0 = (int)y_first, a1 = (int)band_rows, a2 = (int)band_pitch, a3 = (int)n_rows;
   // Tile order: reuse the measured order for this exact geometry, else calibrate on this launch.
   const size_t n_tiles = (size_t)tiles_x * (size_t)tiles_y;
+  // a two-eye scene (stereoscopic, anaglyph): one launch of the view megakernel over both eyes' tiles
+  if (c->views.kind)
+    return launch_views(c, st, a0, a1, a2, a3, max_depth, target, tstride, f64, rgbi, dev_out ? nullptr : out, stride,
+                        row_bytes);
   if (c->kernel_opt == RT_KERNEL_WAVEFRONT) {
     if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
     int rc = launch_wavefront(c, st, a0, a1, a2, a3, max_depth, target, tstride, f64, rgbi, n_tiles);
@@ -145,7 +149,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
     }
     return RT_OK;
   }
-  const int32_t key[7] = {a0, a1, a2, a3, max_depth, f64 ? 1 : 0, c->dev.width};
+  const int32_t key[8] = {a0, a1, a2, a3, max_depth, f64 ? 1 : 0, c->dev.width, RT_CAMERA_PERSPECTIVE};
   const bool refr = c->dev.any_transparent != 0;
   // Kernel choice for scenes without a transparent object (RT_DEFERRED_MAX_TILES): the per-lane
   // megakernel is fastest when the launch fills the GPU many times over (throughput-bound); a

@@ -397,6 +397,7 @@ int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double 
                  uint64_t* rays_traced, void* stream) {
   if (!c || !src_rgba8 || (!dst_rgba8 && !dst_f64)) return fail(RT_ERR_INVALID, "null argument");
   if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
+  if (c->views.kind) return fail(RT_ERR_UNSUPPORTED, "rt_antialias is not built for a two-eye scene (stereoscopic / anaglyph camera)");
   if (level < 0) level = 0;
   if (level > RT_AA_MAX_LEVEL) return fail(RT_ERR_UNSUPPORTED, "anti-aliasing level %d > %d", level, RT_AA_MAX_LEVEL);
   if (!(threshold == threshold)) return fail(RT_ERR_INVALID, "threshold is NaN");
@@ -547,6 +548,7 @@ int rt_record_rays(rt_ctx* c, double x, double y, int32_t max_depth, rt_ray_reco
                    int32_t* n_rays, double* rgba) {
   if (!c || (!records && cap > 0) || cap < 0 || !n_rays) return fail(RT_ERR_INVALID, "null argument");
   if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
+  if (c->views.kind) return fail(RT_ERR_UNSUPPORTED, "rt_record_rays is not built for a two-eye scene (stereoscopic / anaglyph camera)");
   if (max_depth < 0) max_depth = c->max_depth;
   if (max_depth > RT_MAX_DEPTH_CAP) return fail(RT_ERR_UNSUPPORTED, "max_depth %d > %d", max_depth, RT_MAX_DEPTH_CAP);
   RT_HIP(hipSetDevice(c->device));

@@ -240,3 +240,24 @@ struct RtDevScene {
   const double* cam_sx;
   const double* cam_sy;
 };
+
+// Two-eye cameras (StereoscopicCamera / AnaglyphCamera, camera.rs:82-205): a frame is rendered as two
+// VIEWS in one launch.  A view is one eye's PerspectiveCamera, that camera's per-column table (cam_sx for
+// the view's own width), the frame column its column 0 lands on, its width in columns and the channels it
+// stores.  The rows (cam_sy, the band layout) are the frame's.  Passed to the view kernels by value, beside
+// RtDevScene (whose layout the perspective kernels keep).
+enum RtViewChannels : int32_t { RT_VIEW_RGBA = 0, RT_VIEW_R = 1, RT_VIEW_GBA = 2 };
+struct RtView {
+  RtCamera cam;
+  const double* cam_sx;             // width entries: ((x / cam.width) - 0.5) * cam.aspect
+  int32_t x0, width;                // frame columns [x0, x0 + width)
+  int32_t tiles_x;                  // ceil(width / RT_TILE_W)
+  int32_t channels;                 // RtViewChannels
+};
+struct RtViews {
+  RtView v[2];                      // in entry order: the launch's tiles are view 0's, then view 1's
+  int32_t kind;                     // rt_camera_kind (rt_abi.h): 1 stereoscopic, 2 anaglyph
+  int32_t stereo_w;                 // stereoscopic: W / 2, the column the left eye's image starts at
+  int32_t tiles0;                   // view 0's tiles in this launch (tiles_x x the launch's tile rows): set per launch
+  int32_t pad;
+};

@@ -1,6 +1,7 @@
 // rt_ctx.h -- the device context behind the C ABI (include/rt_abi.h: rt_ctx_*), shared by the
 // host halves of the kernel translation units: rt_ctx.hip (create / upload / options / streams),
-// k_rows.hip (the row kernels' launches), k_wavefront.hip, k_views.hip.  Host code only.
+// k_rows.hip (the row kernels' launches), k_stereo.hip (two-eye scenes' launches), k_wavefront.hip,
+// k_views.hip.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +21,7 @@ struct rt_ctx {
   void* d_blob = nullptr;
   size_t blob_bytes = 0;
   RtDevScene dev;
+  RtViews views = {};                   // two-eye scenes (views.kind != 0): the two views' cameras and column tables
   int32_t max_depth = 10;
   int32_t kernel_opt = RT_KERNEL_AUTO;  // rt_ctx_set_option(RT_OPT_KERNEL)
   bool timing = true;                   // rt_ctx_set_option(RT_OPT_TIMING): launch events recorded
@@ -52,7 +54,7 @@ struct rt_ctx {
   // exists, so launches queued on other streams can never read a half-written order; tables are
   // freed only by hipFree (which waits for the device) on eviction, upload or rt_ctx_free.
   struct OrderSlot {
-    int32_t key[7] = {0};
+    int32_t key[8] = {0};             // y_first, band_rows, band_pitch, n_rows, depth, f64, width, camera kind
     int32_t* d_order = nullptr;
     uint32_t* d_cost = nullptr;
     size_t n_tiles = 0;
@@ -107,6 +109,8 @@ struct rt_ctx {
                                         // table folded at compile time: the walks of a program without masks), for
                                         // launches that take no table; reflection-only single-scene programs only
   hipFunction_t spec_def[2][2] = {};    // [f64][cal]
+  hipFunction_t spec_views[2][2] = {};  // [f64][cal]: the view megakernel (two-eye scenes; their programs hold nothing else)
+  bool spec_two_eyes = false;           // the program is a two-eye scene's (spec_flags): view kernels only
   hipFunction_t spec_prim[2][2] = {};   // [f64][cal]: the primary-ray kernel (max_depth 0 launches)
   uint64_t spec_hash = 0;               // FNV-1a of the prelude (kernel info only; caches compare full texts)
   double spec_compile_ms = 0.0;         // the hipRTC time of the loaded programs (0: read from the disk cache)
@@ -171,6 +175,10 @@ bool diag_env(const char* name);
 // k_wavefront.hip: the wavefront path for rows (y_first, band_rows, band_pitch, n_rows) = a0..a3
 int launch_wavefront(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, int max_depth, uint8_t* target,
                      size_t tstride, bool f64, int rgbi, size_t n_tiles, int retry = 0);
+// k_stereo.hip: a two-eye scene's row launch (launch_bands' arguments after its checks; out / stride = the
+// caller's buffer when it is host memory, target the context's scratch then)
+int launch_views(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, int max_depth, uint8_t* target, size_t tstride,
+                 bool f64, int rgbi, void* host_out, size_t host_stride, size_t row_bytes);
 // Completion marks (rt_ctx.hip): record one after every launch of the context on stream st; wait for all
 int mark_event(rt_ctx* c, hipStream_t st, hipEvent_t* ev);   // the event a launch on st binds as its stop event
 int mark_launch(rt_ctx* c, hipStream_t st);                  // record it after work enqueued on st (other launches)

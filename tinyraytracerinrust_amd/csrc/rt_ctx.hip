@@ -170,6 +170,30 @@ int rt_ctx_upload(rt_ctx* c, const rt_scene* s) {
   for (size_t x = 0; x < csx.size(); ++x) csx[x] = (((double)x / f.cam.width) - 0.5) * f.cam.aspect;
   for (size_t y = 0; y < csy.size(); ++y) csy[y] = (f.cam.height - 1.0 - (double)y) / f.cam.height - 0.5;
   size_t o_csx = put(blob, csx), o_csy = put(blob, csy);
+  // Two-eye scenes (rt_blob.h RtViews): each view's column table, the same expressions with the eye
+  // camera's width and aspect ratio.  Stereoscopic (camera.rs:124-128): the RIGHT eye fills columns
+  // [0, w), w = W / 2, the left eye [w, W) at x - w -- for odd W its last column is x - w = w, one past
+  // the eye cameras' nominal width, which create_ray defines all the same.  Anaglyph (:186-195): both
+  // eyes cover the frame, the left stores R, the right G, B and A.
+  RtViews views = {};
+  size_t o_vsx[2] = {0, 0};
+  if (f.cam_kind != RT_CAMERA_PERSPECTIVE) {
+    const bool stereo = f.cam_kind == RT_CAMERA_STEREOSCOPIC;
+    const int32_t w = f.width / 2;
+    views.kind = f.cam_kind;
+    views.stereo_w = w;
+    for (int i = 0; i < 2; ++i) {
+      RtView& v = views.v[i];
+      v.cam = stereo ? f.eye[1 - i] : f.eye[i];
+      v.x0 = stereo && i == 1 ? w : 0;
+      v.width = !stereo ? f.width : i == 0 ? w : f.width - w;
+      v.tiles_x = (v.width + RT_TILE_W - 1) / RT_TILE_W;
+      v.channels = stereo ? RT_VIEW_RGBA : i == 0 ? RT_VIEW_R : RT_VIEW_GBA;
+      std::vector<double> vsx((size_t)std::max(0, v.width));
+      for (size_t x = 0; x < vsx.size(); ++x) vsx[x] = (((double)x / v.cam.width) - 0.5) * v.cam.aspect;
+      o_vsx[i] = put(blob, vsx);
+    }
+  }
   bool masks_ok = false;
   const size_t o_mask = rt::put_mask_scene(f, blob, &masks_ok);
   RT_HIP(hipSetDevice(c->device));
@@ -212,6 +236,9 @@ int rt_ctx_upload(rt_ctx* c, const rt_scene* s) {
   d.shadow_pow = f.shadow_pow;
   d.shadow_t = f.shadow_t;
   d.cam = f.cam;
+  const int32_t prev_kind = c->views.kind;
+  c->views = views;
+  for (int i = 0; i < 2 && views.kind; ++i) c->views.v[i].cam_sx = (const double*)(b + o_vsx[i]);
   c->max_depth = f.max_depth;
   {                                   // the wavefront path's key extent: the hull of the bounded objects
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -233,7 +260,9 @@ int rt_ctx_upload(rt_ctx* c, const rt_scene* s) {
   // calibration variant at the default level (a calibrating launch would run the generic kernels).
   // The ray-tree scenes' wavefront / megakernel choice is measured again (reset_order_choices); the tile
   // masks, which depend on the camera and on every position, were dropped above whatever the structure.
-  if (!(c->spec_flat && rt::same_structure_flat(*c->spec_flat, f))) drop_orders(c);
+  // The camera kind counts as structure here: a two-eye launch has other tiles (two views') and other
+  // kernels, and an upload of a perspective scene after a two-eye one behaves as on a fresh context.
+  if (!(c->spec_flat && prev_kind == f.cam_kind && rt::same_structure_flat(*c->spec_flat, f))) drop_orders(c);
   else rt::reset_order_choices(c);
   // the scene-specialised programs (spec.hip): requested from the compile pool, loaded by the first
   // launch after they are ready; the generic kernels render until then.  Only the flags are computed

@@ -1868,6 +1868,61 @@ __device__ __forceinline__ void rows_body(const RtDevScene& S, int y_first, int 
   rows_entry<MODE, F64, CAL, FC, KL_, KP_, PRIM>(S, blockIdx.x, y_first, band_rows, band_pitch, n_rows, max_depth, out,
                                                  stride, order, cost, rgb, frames, masks);
 }
+// Two-eye cameras (StereoscopicCamera / AnaglyphCamera, camera.rs:82-205; rt_blob.h RtViews): one launch
+// over the tiles of two views.  Entry e (or the order's e-th) is tile e of view 0 for e < tiles0, else
+// tile e - tiles0 of view 1; the wave's camera and column table are its view's (wave-uniform), the rows
+// and everything past the primary ray are rows_entry's.  The walks take no tile masks.
+// A view stores the channels it owns (anaglyph: the left eye R, the right eye G, B and A -- disjoint bytes
+// of one pixel, so the two eyes' waves need no order and every output byte is written once): RGBA8 as a
+// byte, or a byte and an aligned 16-bit B | 255 << 8; RGB8 as bytes; f64 as o[0] or o[1..3].
+template <bool F64>
+__device__ __forceinline__ void store_pixel_view(uint8_t* row, int x, Col c, int rgb, int channels) {
+  if (channels == RT_VIEW_RGBA) {
+    store_pixel<F64>(row, x, c, rgb);
+  } else if constexpr (F64) {
+    double* o = (double*)row + (size_t)x * 4;
+    if (channels == RT_VIEW_R) o[0] = c.r;
+    else { o[1] = c.g; o[2] = c.b; o[3] = 1.0; }
+  } else if (rgb) {
+    uint8_t* o = row + (size_t)x * 3;
+    if (channels == RT_VIEW_R) frame_store((uint8_t)to_u8(c.r), o);
+    else { frame_store((uint8_t)to_u8(c.g), o + 1); frame_store((uint8_t)to_u8(c.b), o + 2); }
+  } else {
+    uint8_t* o = row + (size_t)x * 4;
+    if (channels == RT_VIEW_R) frame_store((uint8_t)to_u8(c.r), o);
+    else { frame_store((uint8_t)to_u8(c.g), o + 1); frame_store((unsigned short)(to_u8(c.b) | (255u << 8)), (unsigned short*)(o + 2)); }
+  }
+}
+template <int MODE, bool F64, bool CAL, bool FC, int KL_ = -1, int KP_ = -1>
+__device__ __forceinline__ void rows_views_body(const RtDevScene& S, const RtViews& VW, int y_first, int band_rows,
+                                                int band_pitch, int n_rows, int max_depth, uint8_t* __restrict__ out,
+                                                size_t stride, const int32_t* __restrict__ order,
+                                                uint32_t* __restrict__ cost, int rgb, lds_f64* frames) {
+  constexpr bool REFR = MODE != RT_MODE_REFL, CHAIN = MODE == RT_MODE_CHAIN;
+  constexpr int KLR = MODE == RT_MODE_TREE ? RT_LDS_RFRAMES : 0;
+  constexpr int KP = rows_pool_slots<MODE, KL_, KP_>();
+  constexpr int KL = rows_lane_frames<MODE, KL_>();
+  const int lane = threadIdx.x & 63;
+  const unsigned entry = CAL || !order ? blockIdx.x : (unsigned)order[blockIdx.x];
+  [[maybe_unused]] uint64_t t_start = 0;
+  if constexpr (CAL) t_start = wall_clock64();
+  const int vi = __builtin_amdgcn_readfirstlane(entry >= (unsigned)VW.tiles0 ? 1 : 0);
+  const RtView& V = VW.v[vi];
+  const unsigned tile = entry - (vi ? (unsigned)VW.tiles0 : 0u);
+  const int xv = (int)(tile % (unsigned)V.tiles_x) * RT_TILE_W + lane % RT_TILE_W;   // the view's own column
+  const int r = (int)(tile / (unsigned)V.tiles_x) * RT_TILE_H + lane / RT_TILE_W;
+  if (xv >= V.width || r >= n_rows) return;
+  const int y = band_row(r, y_first, band_rows, band_pitch, n_rows);
+  if (y >= S.height) return;
+  const double sx = V.cam_sx[xv], sy = S.cam_sy[y];                          // create_ray(xv as f64, y as f64)
+  const V3 rd = add(add(ld3(V.cam.direction), scale(ld3(V.cam.right), sx)), scale(ld3(V.cam.up), sy));
+  const V3 ro = ld3(V.cam.center);
+  const Col c = trace<REFR, NoRec, KL, FC, KLR, CHAIN, KP>(make_ds(S), ro, rd, max_depth, nullptr, frames + lane, frames,
+                                                         nullptr);
+  store_pixel_view<F64>(out + (size_t)r * stride, V.x0 + xv, c, rgb, V.channels);
+  if constexpr (CAL)
+    if (threadIdx.x == 0) cost[entry] = (uint32_t)(wall_clock64() - t_start);   // vector store
+}
 template <int MODE, int KL_ = -1, int KP_ = -1>
 constexpr int rows_lds_doubles() {
   return (rows_lane_frames<MODE, KL_>() * 4 + (MODE == RT_MODE_TREE ? RT_LDS_RFRAMES : 0) * 7) * 64 +

@@ -710,6 +710,10 @@ std::string describe_flat(const FlatScene& f) {
   };
   emit("scene any_transparent=%d ray_chains=%d colour_fast=%d shadow_early_out=%d shadow_pow=%d\n",
           f.any_transparent, f.ray_chains, f.colour_fast, f.shadow_early_out, f.shadow_pow);
+  if (f.cam_kind != RT_CAMERA_PERSPECTIVE)
+    emit("camera %s eye_distance=%.17g left [%.17g %.17g %.17g] right [%.17g %.17g %.17g]\n",
+         f.cam_kind == RT_CAMERA_STEREOSCOPIC ? "stereoscopic" : "anaglyph", f.eye_distance, f.eye[0].center[0],
+         f.eye[0].center[1], f.eye[0].center[2], f.eye[1].center[0], f.eye[1].center[1], f.eye[1].center[2]);
   for (size_t i = 0; i < f.trav.size(); ++i)
     emit("trav %zu obj=%d skip=%d box [%.3f %.3f %.3f]..[%.3f %.3f %.3f]\n", i, f.trav[i].obj, f.trav[i].skip,
             f.trav[i].blo[0], f.trav[i].blo[1], f.trav[i].blo[2], f.trav[i].bhi[0], f.trav[i].bhi[1], f.trav[i].bhi[2]);
@@ -899,19 +903,35 @@ int flatten(const rt_scene& s, FlatScene* out) {
     while (off % 16) { f.texels.push_back(0); ++off; }
   }
   // PerspectiveCamera::new(width, height, center, None, None, None) (camera.rs:30-54)
-  V center = {s.cam_center[0], s.cam_center[1], s.cam_center[2]};
-  V look_at = {0.0, 0.0, 0.0}, up = {0.0, 1.0, 0.0}, right = {0.0, 0.0, 0.0};
-  V direction = normalized(sub(look_at, center));
-  double aspect = (double)s.width / (double)s.height;
-  if (length(right) == 0.0) { V c = cross(direction, up); right = {-c.x, -c.y, -c.z}; }
-  RtCamera& cam = f.cam;
-  cam.center[0] = center.x; cam.center[1] = center.y; cam.center[2] = center.z;
-  cam.direction[0] = direction.x; cam.direction[1] = direction.y; cam.direction[2] = direction.z;
-  cam.right[0] = right.x; cam.right[1] = right.y; cam.right[2] = right.z;
-  cam.up[0] = up.x; cam.up[1] = up.y; cam.up[2] = up.z;
-  cam.aspect = aspect;
-  cam.width = (double)s.width;
-  cam.height = (double)s.height;
+  auto perspective = [](V center, uint32_t width, uint32_t height, RtCamera& cam) {
+    V look_at = {0.0, 0.0, 0.0}, up = {0.0, 1.0, 0.0}, right = {0.0, 0.0, 0.0};
+    V direction = normalized(sub(look_at, center));
+    double aspect = (double)width / (double)height;
+    if (length(right) == 0.0) { V c = cross(direction, up); right = {-c.x, -c.y, -c.z}; }
+    cam.center[0] = center.x; cam.center[1] = center.y; cam.center[2] = center.z;
+    cam.direction[0] = direction.x; cam.direction[1] = direction.y; cam.direction[2] = direction.z;
+    cam.right[0] = right.x; cam.right[1] = right.y; cam.right[2] = right.z;
+    cam.up[0] = up.x; cam.up[1] = up.y; cam.up[2] = up.z;
+    cam.aspect = aspect;
+    cam.width = (double)width;
+    cam.height = (double)height;
+  };
+  perspective({s.cam_center[0], s.cam_center[1], s.cam_center[2]}, s.width, s.height, f.cam);
+  // StereoscopicCamera::new / AnaglyphCamera::new (camera.rs:90-120, :152-181): `right` is the scene
+  // camera's (the same -cross(normalize(look_at - center), up)); the eyes sit half the eye distance to
+  // either side of the centre along it, each a PerspectiveCamera of its own looking at the origin (its
+  // direction and right recomputed from the eye).  The stereoscopic eyes are built at width / 2.
+  f.cam_kind = s.cam_kind;
+  f.eye_distance = s.eye_distance;
+  f.eye[0] = f.eye[1] = f.cam;
+  if (s.cam_kind != RT_CAMERA_PERSPECTIVE) {
+    const double h = s.eye_distance / 2.0;
+    const uint32_t w = s.cam_kind == RT_CAMERA_STEREOSCOPIC ? s.width / 2 : s.width;
+    const double* C = f.cam.center;
+    const double* R = f.cam.right;
+    perspective({C[0] - R[0] * h, C[1] - R[1] * h, C[2] - R[2] * h}, w, s.height, f.eye[0]);   // left_eye
+    perspective({C[0] + R[0] * h, C[1] + R[1] * h, C[2] + R[2] * h}, w, s.height, f.eye[1]);   // right_eye
+  }
   return RT_OK;
 }
 
@@ -1107,6 +1127,41 @@ int rt_scene_get_camera(const rt_scene* s, double out[13]) {
     out[i] = f.cam.center[i]; out[3 + i] = f.cam.direction[i]; out[6 + i] = f.cam.right[i]; out[9 + i] = f.cam.up[i];
   }
   out[12] = f.cam.aspect;
+  return RT_OK;
+}
+int rt_scene_set_camera_kind(rt_scene* s, int32_t kind, double eye_distance) {
+  if (!s) return fail(RT_ERR_INVALID, "null scene");
+  if (kind != RT_CAMERA_PERSPECTIVE && kind != RT_CAMERA_STEREOSCOPIC && kind != RT_CAMERA_ANAGLYPH)
+    return fail(RT_ERR_INVALID, "unknown camera kind %d", kind);
+  if (!std::isfinite(eye_distance)) return fail(RT_ERR_INVALID, "eye distance is not finite");
+  if (kind == RT_CAMERA_STEREOSCOPIC && s->width < 2)
+    return fail(RT_ERR_INVALID, "a stereoscopic camera needs a frame at least 2 pixels wide (width %u)", s->width);
+  s->cam_kind = kind;
+  s->eye_distance = eye_distance;
+  return RT_OK;
+}
+int rt_scene_get_camera_kind(const rt_scene* s, int32_t* kind, double* eye_distance) {
+  if (!s) return fail(RT_ERR_INVALID, "null scene");
+  if (kind) *kind = s->cam_kind;
+  if (eye_distance) *eye_distance = s->eye_distance;
+  return RT_OK;
+}
+int rt_scene_get_camera_eye(const rt_scene* s, int32_t eye, double out[13]) {
+  if (!s || !out) return fail(RT_ERR_INVALID, "null argument");
+  if (eye < 0 || eye > 1) return fail(RT_ERR_INVALID, "eye %d not in 0..1", eye);
+  if (s->cam_kind == RT_CAMERA_PERSPECTIVE) return fail(RT_ERR_INVALID, "a perspective scene has no eye cameras");
+  FlatScene f;
+  rt_scene tmp;                                       // camera only, as rt_scene_get_camera
+  tmp.width = s->width; tmp.height = s->height;
+  memcpy(tmp.cam_center, s->cam_center, sizeof tmp.cam_center);
+  tmp.cam_kind = s->cam_kind; tmp.eye_distance = s->eye_distance;
+  int rc = flatten(tmp, &f);
+  if (rc) return rc;
+  const RtCamera& cam = f.eye[eye];
+  for (int i = 0; i < 3; ++i) {
+    out[i] = cam.center[i]; out[3 + i] = cam.direction[i]; out[6 + i] = cam.right[i]; out[9 + i] = cam.up[i];
+  }
+  out[12] = cam.aspect;
   return RT_OK;
 }
 int rt_scene_get_light(const rt_scene* s, int32_t i, double point[3], double color[4]) {

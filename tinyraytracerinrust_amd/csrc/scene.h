@@ -49,6 +49,9 @@ struct FlatScene {
   std::vector<RtTexture> textures;
   std::vector<uint8_t> texels;
   RtCamera cam;
+  int32_t cam_kind = 0;           // rt_camera_kind; eye[] = the left and right eye's cameras (camera.rs:108-112),
+  double eye_distance = 0.0;      // copies of cam for a perspective scene
+  RtCamera eye[2];
   int32_t width, height, max_depth;
   int32_t any_transparent, shadow_early_out;
   int32_t colour_fast;   // every colour-op operand is finite and >= +0 (see flatten)
@@ -71,6 +74,8 @@ struct rt_scene {
   uint32_t width = 0, height = 0;
   int32_t max_depth = 10;
   double cam_center[3] = {0.0, 0.0, -100.0};
+  int32_t cam_kind = RT_CAMERA_PERSPECTIVE;   // rt_scene_set_camera_kind: the eyes are derived from cam_center by flatten
+  double eye_distance = 0.0;
   std::vector<rt::ShapeRec> shapes;
   std::vector<rt::ObjectRec> objects;
   std::vector<rt::LightRec> lights;

@@ -315,7 +315,16 @@ static std::string spec_kernel(int kind, int mode, bool fc, int f64, int cal) {
   if (const char* e = getenv("RT_SPEC_KL")) kl = atoi(e);      // diagnostic builds: A/B of the LDS frames
   if (const char* e = getenv("RT_SPEC_KP")) kp = atoi(e);
 #endif
-  if (kind == 2)                                              // the primary-ray kernel (rt_device.h PRIM)
+  if (kind == 4)                                              // a two-eye scene's view megakernel (rt_device.h rows_views_body)
+    snprintf(buf, sizeof buf,
+             "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(%s))) "
+             "void rt_spec_views_%d%d(RtDevScene S, RtViews VW, int y_first, int band_rows, int band_pitch, int n_rows, "
+             "int max_depth, uint8_t* __restrict__ out, size_t stride, const int32_t* __restrict__ order, "
+             "uint32_t* __restrict__ cost, int rgb) {\n  __shared__ double s_frames[rows_lds_doubles<%d, %d, %d>()];\n"
+             "  rows_views_body<%d, %s, %s, %s, %d, %d>(S, VW, y_first, band_rows, band_pitch, n_rows, max_depth, out, stride, "
+             "order, cost, rgb, (lds_f64*)s_frames);\n}\n",
+             waves, f64, cal, mode, kl, kp, mode, f64 ? "true" : "false", cal ? "true" : "false", fc ? "true" : "false", kl, kp);
+  else if (kind == 2)                                         // the primary-ray kernel (rt_device.h PRIM)
     snprintf(buf, sizeof buf,
              "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(%d))) "
              "void rt_spec_prim_%d%d%s {\n"
@@ -347,10 +356,18 @@ static std::string spec_kernel(int kind, int mode, bool fc, int f64, int cal) {
 // f64 and calibration instantiations too (tests: every launch of a parity test then runs specialised).
 // Each kernel is its own program (prelude + one kernel): the programs compile in parallel, and the
 // inliner sees one kernel per module.
+// A two-eye scene's program (rt_ctx::spec_two_eyes) holds kind 4 only, the view megakernel with mask-free
+// walks: every launch of such a scene takes it, and a perspective scene's program holds none.  The camera
+// reaches the kernels as an argument, so the prelude -- and the program -- does not depend on the eyes.
 struct SpecKernel { int kind, f64, cal; };
 static std::vector<SpecKernel> spec_kernels(const rt_ctx* c, bool with_nm) {
   std::vector<SpecKernel> v;
   const int n = c->spec_on >= 2 ? 2 : 1;
+  if (c->spec_two_eyes) {
+    for (int f64 = 0; f64 < n; ++f64)
+      for (int cal = 0; cal < n; ++cal) v.push_back({4, f64, cal});
+    return v;
+  }
   for (int kind = 0; kind < 3; ++kind) {
     if (kind == 1 && !c->spec_deferred) continue;
     for (int f64 = 0; f64 < n; ++f64)
@@ -368,14 +385,14 @@ static std::vector<SpecKernel> spec_kernels(const rt_ctx* c, bool with_nm) {
   return v;
 }
 static const char* spec_kernel_name(int kind) {
-  return kind == 2 ? "rt_spec_prim_%d%d" : kind == 1 ? "rt_spec_def_%d%d" : "rt_spec_rows_%d%d";   // kinds 0 and 3
+  return kind == 4 ? "rt_spec_views_%d%d" : kind == 2 ? "rt_spec_prim_%d%d" : kind == 1 ? "rt_spec_def_%d%d" : "rt_spec_rows_%d%d";   // kinds 0 and 3
 }
 static std::vector<std::string> spec_programs(const rt_ctx* c, bool with_nm = false) {
   std::vector<std::string> v;
   // kind 3 (the mask-free megakernel) is a program compiled with RT_TILE_MASKS 0: the device code without the
   // mask operand, not merely a null table
   for (const SpecKernel& k : spec_kernels(c, with_nm))
-    v.push_back((k.kind == 3 ? "#define RT_TILE_MASKS 0\n" : "") + c->spec_src + spec_kernel(k.kind, c->spec_mode, c->spec_fc, k.f64, k.cal));
+    v.push_back((k.kind == 3 || k.kind == 4 ? "#define RT_TILE_MASKS 0\n" : "") + c->spec_src + spec_kernel(k.kind, c->spec_mode, c->spec_fc, k.f64, k.cal));
   return v;
 }
 
@@ -613,7 +630,8 @@ int spec_compile(const std::string& src, SpecCode* out, std::string* err) {
 
 int spec_guard(const SpecCode& c, const std::string& text, std::string* err) {
   const bool def = c.name.rfind("rt_spec_def_", 0) == 0;
-  const bool tree = text.find("rows_body<" + std::to_string(RT_MODE_TREE) + ",") != std::string::npos;
+  const bool tree = text.find("rows_body<" + std::to_string(RT_MODE_TREE) + ",") != std::string::npos ||
+                    text.find("rows_views_body<" + std::to_string(RT_MODE_TREE) + ",") != std::string::npos;
   const int max_scratch = def ? RT_SPEC_MAX_SCRATCH_DEF : tree ? RT_SPEC_MAX_SCRATCH_TREE : RT_SPEC_MAX_SCRATCH_ROWS;
   if (c.name.empty() || c.vgprs < 0 || c.scratch < 0) {
     *err = "resource guard: the code object's metadata holds no resource usage for the kernel";
@@ -801,7 +819,8 @@ void spec_flags(const FlatScene& f, rt_ctx* c) {
   c->spec_fits = f.objects.size() <= RT_SPEC_MAX_OBJECTS && f.leaves.size() <= RT_SPEC_MAX_LEAVES;
   c->spec_mode = !f.any_transparent ? RT_MODE_REFL : f.ray_chains ? RT_MODE_CHAIN : RT_MODE_TREE;
   c->spec_fc = f.colour_fast != 0;
-  c->spec_deferred = c->spec_mode == RT_MODE_REFL;
+  c->spec_two_eyes = f.cam_kind != RT_CAMERA_PERSPECTIVE;
+  c->spec_deferred = c->spec_mode == RT_MODE_REFL && !c->spec_two_eyes;
 }
 
 // The program text of a flattened scene for c's level: a registered family's, or its own.
@@ -829,6 +848,7 @@ void spec_drop(rt_ctx* c) {
   memset(c->spec_rows_nm, 0, sizeof c->spec_rows_nm);
   memset(c->spec_def, 0, sizeof c->spec_def);
   memset(c->spec_prim, 0, sizeof c->spec_prim);
+  memset(c->spec_views, 0, sizeof c->spec_views);
   c->spec_jobs.clear();                                   // drops this context's interest
   c->spec_error.clear();
 }
@@ -870,7 +890,7 @@ int spec_poll(rt_ctx* c) {
     hipError_t e = hipModuleLoadData(&c->spec_mods[i], code.code.data());
     if (e == hipSuccess) {
       snprintf(name, sizeof name, spec_kernel_name(k.kind), k.f64, k.cal);
-      hipFunction_t* fn = k.kind == 3 ? &c->spec_rows_nm[k.f64][k.cal] : k.kind == 2 ? &c->spec_prim[k.f64][k.cal]
+      hipFunction_t* fn = k.kind == 4 ? &c->spec_views[k.f64][k.cal] : k.kind == 3 ? &c->spec_rows_nm[k.f64][k.cal] : k.kind == 2 ? &c->spec_prim[k.f64][k.cal]
                           : k.kind ? &c->spec_def[k.f64][k.cal] : &c->spec_rows[k.f64][k.cal];
       e = hipModuleGetFunction(fn, c->spec_mods[i], name);
     }

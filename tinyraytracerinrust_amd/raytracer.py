@@ -226,6 +226,25 @@ class Scene:
         v = list(out)
         return {"center": v[0:3], "direction": v[3:6], "right": v[6:9], "up": v[9:12], "aspect": v[12]}
 
+    def set_camera_kind(self, kind: str, eye_distance: float = 0.0) -> None:
+        """rt_scene_set_camera_kind: "perspective", "stereoscopic" (camera.rs:82-141) or "anaglyph" (:143-205)."""
+        if kind not in _lib.CAMERA_KINDS:
+            raise ValueError(f"camera kind {kind!r} not in {sorted(_lib.CAMERA_KINDS)}")
+        check(lib().rt_scene_set_camera_kind(self.h, _lib.CAMERA_KINDS[kind], float(eye_distance)))
+
+    def camera_kind(self) -> Tuple[str, float]:
+        """(kind, eye_distance) as set_camera_kind took them; ("perspective", 0.0) by default."""
+        k, d = ctypes.c_int32(), ctypes.c_double()
+        check(lib().rt_scene_get_camera_kind(self.h, ctypes.byref(k), ctypes.byref(d)))
+        return {v: n for n, v in _lib.CAMERA_KINDS.items()}[k.value], d.value
+
+    def camera_eye(self, i: int) -> dict:
+        """Eye i (0 left, 1 right) of a stereoscopic / anaglyph scene, as camera()."""
+        out = (ctypes.c_double * 13)()
+        check(lib().rt_scene_get_camera_eye(self.h, int(i), out))
+        v = list(out)
+        return {"center": v[0:3], "direction": v[3:6], "right": v[6:9], "up": v[9:12], "aspect": v[12]}
+
     def light(self, i: int) -> Tuple[list, list]:
         p, c = (ctypes.c_double * 3)(), (ctypes.c_double * 4)()
         check(lib().rt_scene_get_light(self.h, i, p, c))
@@ -515,6 +534,7 @@ class RayTracer:
         self._renderer: Optional[Renderer] = None
         self._dirty = True
         self._max_depth = 10
+        self._camera_kind = ("perspective", 0.0)
 
     new_default = classmethod(lambda cls, width, height, device=0: cls(width, height, device))
 
@@ -570,14 +590,30 @@ class RayTracer:
         self._max_depth = int(d)
         self._dirty = True
 
+    def set_camera_kind(self, kind: str, eye_distance: float = 0.0) -> None:
+        """The scene's Camera: "perspective" (the default), "stereoscopic" (camera.rs:82-141, two eyes side
+        by side) or "anaglyph" (:143-205, red from the left eye, green and blue from the right).  Kept, like
+        max_depth, across load_scene."""
+        self.scene.set_camera_kind(kind, eye_distance)
+        self._camera_kind = (kind, float(eye_distance))
+        self._dirty = True
+
     def load_scene(self, text: str, time: float = 0.0, asset_dir: Optional[str] = None,
-                   strict: bool = True) -> None:
+                   strict: bool = True, camera_kind: Optional[str] = None,
+                   eye_distance: Optional[float] = None) -> None:
         """DebugWindow::load_ray_tracer (debug_window.rs:53-62): a fresh new_default RayTracer
-        with the test light, then load_scene(text, time).  Replaces this tracer's scene."""
+        with the test light, then load_scene(text, time).  Replaces this tracer's scene.
+        camera_kind / eye_distance: set_camera_kind on the new scene (the DSL has no syntax for it)."""
+        if camera_kind is not None:
+            if camera_kind != "perspective" and eye_distance is None:
+                raise ValueError(f"camera kind {camera_kind!r} needs an eye_distance")
+            self._camera_kind = (camera_kind, float(eye_distance or 0.0))
         self.scene = Scene.compile(text, time, self.width, self.height, asset_dir, strict)
         self.transformation_stack = TransformationStack()
         if self._max_depth != 10:
             check(lib().rt_scene_set_max_depth(self.scene.h, self._max_depth))
+        if self._camera_kind[0] != "perspective":
+            self.scene.set_camera_kind(*self._camera_kind)
         self._dirty = True
 
     # -- rendering ------------------------------------------------------------------------
