@@ -327,10 +327,19 @@ int rt_ctx_synchronize(rt_ctx* ctx);
  * Two-eye scenes (rt_scene_set_camera_kind) always take the view megakernels (k_stereo.hip: one launch over
  * the tiles of both eyes, mask-free walks): RT_KERNEL_DEFERRED, RT_KERNEL_WAVEFRONT and RT_OPT_TILE_MASKS have
  * no effect on them; RT_OPT_TILE_ORDER and RT_OPT_SPECIALIZE apply (rt_ctx_kernel_info says which kernel ran).
+ * RT_OPT_SPEC_SAMPLES: 1 (default) lets rt_render_points_f64 and rt_antialias' trace passes take specialised
+ * kernels too (the sample programs rt_spec_points / rt_spec_aa: the uploaded scene's tables as constants, the
+ * megakernel's frame storage, mask-free walks).  They are a second set of programs beside the row programs:
+ * the first points / anti-aliasing call after an upload requests them (a context that asked once requests them
+ * with every later upload, behind the row programs in the compile pool), the generic kernels run until they
+ * are loaded, and each path loads or fails on its own (rt_ctx_sample_kernel_info says which runs and why;
+ * rt_ctx_spec_wait_samples blocks for them).  They apply where RT_OPT_SPECIALIZE does and the camera is
+ * perspective; two-eye scenes and scenes above the specialisation limits keep the generic kernels.  0: the
+ * sample paths always run generic.  Same samples, bit for bit.
  * Option 7 is retired (round 4's tail kernel, measured slower than the launch it shortened). */
 typedef enum rt_option {
   RT_OPT_KERNEL = 0, RT_OPT_TIMING = 1, RT_OPT_TILE_ORDER = 2, RT_OPT_FAST_CLAMP = 3, RT_OPT_WAVEFRONT_CAP = 4,
-  RT_OPT_WAVEFRONT_PAIRS = 5, RT_OPT_SPECIALIZE = 6, RT_OPT_TILE_MASKS = 8
+  RT_OPT_WAVEFRONT_PAIRS = 5, RT_OPT_SPECIALIZE = 6, RT_OPT_TILE_MASKS = 8, RT_OPT_SPEC_SAMPLES = 9
 } rt_option;
 typedef enum rt_kernel_choice {
   RT_KERNEL_AUTO = 0, RT_KERNEL_MEGA = 1, RT_KERNEL_DEFERRED = 2, RT_KERNEL_WAVEFRONT = 3
@@ -358,6 +367,20 @@ int rt_scene_tile_masks(const rt_scene* scene, uint32_t y_first, uint32_t band_r
  * the limit passed first; a negative status: the compile failed or the guard refused it (the
  * context keeps the generic kernels, rt_last_error / rt_ctx_kernel_info say why). */
 int rt_ctx_spec_wait(rt_ctx* ctx, int32_t timeout_ms);
+/* The same for the sample programs (RT_OPT_SPEC_SAMPLES): requests them if the context has not yet, waits at
+ * most timeout_ms (< 0: no limit) and loads them.  RT_OK: both loaded, or nothing to wait for (an option off,
+ * scene too large, two-eye scene); RT_PENDING: the limit passed first; a negative status: a compile failed or
+ * the guard refused it (that path keeps the generic kernel; the row programs are not affected). */
+int rt_ctx_spec_wait_samples(rt_ctx* ctx, int32_t timeout_ms);
+/* What the sample paths run, as text: "points: generic (REASON)" or "points: specialised (rt_spec_points of
+ * hipRTC HASH, V VGPRs (S spilled), B B/lane scratch, compiled in T ms [process cache | disk cache])", the
+ * same for "aa trace", then "; last sample launch: " and "points (specialised)", "points", "aa trace
+ * (specialised)", "aa trace" or "none". */
+int rt_ctx_sample_kernel_info(rt_ctx* ctx, char* buf, size_t cap);
+/* The two sample programs of a scene compiled (or found) without a device, as rt_scene_spec_report does for
+ * the row programs: one line per kernel (rt_spec_points, rt_spec_aa) in that call's "NAME: field value ..."
+ * format.  RT_ERR_UNSUPPORTED: a scene above the specialisation limits, or a two-eye scene. */
+int rt_scene_sample_report(const rt_scene* scene, char* buf, size_t cap, size_t* len);
 /* Compile the scene's specialised program (RT_OPT_SPECIALIZE) into the process's code-object
  * cache without a device, so a later upload of the same scene finds it; *compile_ms = the hipRTC
  * time (0 when it was cached already).  May run on any thread. */

@@ -411,6 +411,12 @@ int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double 
   if (dst_f64 && f64_stride < row32) return fail(RT_ERR_INVALID, "f64 stride %zu < %zu", f64_stride, row32);
   RT_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
+  // the trace passes' kernel: the scene's specialised one once it is loaded (requested here on the first call
+  // after an upload, polled without blocking); last_sample names it only if a pass launches
+  const char* const sample_before = c->last_sample;
+  const hipFunction_t sfn = spec_sample_kernel(c, RT_SAMPLE_AA);
+  const char* const sample_ran = c->last_sample;
+  c->last_sample = sample_before;
   const size_t npx = (size_t)W * H;
   // device staging: [src u8][dst u8][dst f64][edges][counters] for host pointers
   const bool d_src = is_device_ptr(src_rgba8), d_u8 = !dst_rgba8 || is_device_ptr(dst_rgba8);
@@ -473,8 +479,18 @@ int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double 
       rays += n_req;
       const dim3 rg((n_req + 63) / 64);
       const bool fc = c->dev.colour_fast != 0 && c->fast_clamp;
+      c->last_sample = sample_ran;
 #define RT_LAUNCH_AA(R, F) hipLaunchKernelGGL((aa_trace_kernel<R, F>), rg, dim3(64), 0, st, c->dev, G, edges, req, n_req, (int)max_depth)
-      if (c->dev.any_transparent && fc) RT_LAUNCH_AA(true, true);
+      if (sfn) {                                                 // the scene's specialised trace kernel (spec.hip rt_spec_aa)
+        int depth = max_depth, size = sz;
+        double* col = (double*)G.col;
+        void* kargs[] = {&c->dev, (void*)&edges, (void*)&req, &n_req, &size, &col, &depth};
+        if (hipModuleLaunchKernel(sfn, rg.x, 1, 1, 64, 1, 1, 0, st, kargs, nullptr) != hipSuccess) {
+          err = fail(RT_ERR_DEVICE, "the specialised anti-aliasing trace kernel failed to launch");
+          break;
+        }
+      }
+      else if (c->dev.any_transparent && fc) RT_LAUNCH_AA(true, true);
       else if (c->dev.any_transparent) RT_LAUNCH_AA(true, false);
       else if (fc) RT_LAUNCH_AA(false, true);
       else RT_LAUNCH_AA(false, false);

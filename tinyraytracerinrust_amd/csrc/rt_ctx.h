@@ -123,6 +123,20 @@ struct rt_ctx {
   std::string spec_res;                 // the loaded megakernel's resources (kernel info)
   double spec_t0 = 0.0;                 // when the programs were requested (steady clock, ms)
   double spec_ready_ms = 0.0;           // request -> loaded, ms
+  // The sample programs (spec.hip rt_spec_points / rt_spec_aa, RT_OPT_SPEC_SAMPLES): the specialised kernels of
+  // rt_render_points_f64 ([0]) and of rt_antialias' trace passes ([1]), a job set of their own beside spec_jobs.
+  // Requested by the first such call after an upload (and by every later upload once a context has asked),
+  // behind the row programs in the pool; each path loads, fails and is reported on its own, and nothing here
+  // touches the row programs' state above.
+  int samp_on = 1;                      // RT_OPT_SPEC_SAMPLES
+  bool samp_wanted = false;             // a points / AA call (or rt_ctx_spec_wait_samples) has asked: uploads request them
+  std::shared_ptr<rt::SpecJob> samp_jobs[2];   // requested, not yet loaded
+  hipModule_t samp_mods[2] = {};
+  hipFunction_t samp_fn[2] = {};        // non-null once loaded (null: the generic kernel)
+  std::string samp_error[2];            // why a path stays generic although requested
+  std::string samp_res[2];              // a loaded kernel's resources, compile time and provenance (sample kernel info)
+  bool samp_cached[2] = {};             // the code object existed in the process when it was requested
+  const char* last_sample = "none";     // what the last points / AA trace launch ran (rt_ctx_sample_kernel_info)
   // Completion marks: per stream this context launched on, an event recorded after its last launch
   // there.  rt_ctx_synchronize / option changes / rt_ctx_free wait on them -- never on a caller's
   // stream, which may be destroyed by then.
@@ -192,4 +206,13 @@ int spec_poll(rt_ctx* c);                           // load them if compiled: RT
 int spec_wait(rt_ctx* c, double timeout_ms);        // block (< 0: no limit) then spec_poll
 void spec_drop(rt_ctx* c);                          // unload + release (no launch of c may be in flight)
 const char* spec_compiler();                        // which hipRTC compiles the programs
+// the sample programs (path 0: points, 1: the anti-aliasing trace)
+enum { RT_SAMPLE_POINTS = 0, RT_SAMPLE_AA = 1 };
+void spec_samples_request(rt_ctx* c, bool retry = false);   // ask the pool for them (no-op where they do not apply)
+void spec_samples_poll(rt_ctx* c);                  // load what has compiled (non-blocking)
+int spec_samples_wait(rt_ctx* c, double timeout_ms);   // request, block (< 0: no limit), load: RT_OK / RT_PENDING
+// The kernel of a points / AA call about to launch (the context's device current): requests the programs on the
+// first call, polls, and returns the loaded kernel or null (the generic one runs); sets last_sample.
+hipFunction_t spec_sample_kernel(rt_ctx* c, int path);
+std::string spec_sample_info(rt_ctx* c);            // rt_ctx_sample_kernel_info's text
 }  // namespace rt

@@ -313,6 +313,22 @@ int rt_ctx_spec_wait(rt_ctx* c, int32_t timeout_ms) {
   return RT_OK;
 }
 
+int rt_ctx_spec_wait_samples(rt_ctx* c, int32_t timeout_ms) {
+  if (!c) return fail(RT_ERR_INVALID, "null context");
+  RT_HIP(hipSetDevice(c->device));
+  if (rt::spec_samples_wait(c, (double)timeout_ms) == RT_PENDING) return RT_PENDING;
+  for (int k = 0; k < 2; ++k)
+    if (!c->samp_error[k].empty())
+      return fail(RT_ERR_UNSUPPORTED, "%s: %s", k == rt::RT_SAMPLE_POINTS ? "rt_spec_points" : "rt_spec_aa", c->samp_error[k].c_str());
+  return RT_OK;
+}
+
+int rt_ctx_sample_kernel_info(rt_ctx* c, char* buf, size_t cap) {
+  if (!c || !buf || cap == 0) return fail(RT_ERR_INVALID, "null argument");
+  snprintf(buf, cap, "%s", rt::spec_sample_info(c).c_str());
+  return RT_OK;
+}
+
 int rt_ctx_last_kernel_ms(rt_ctx* c, float* ms) {
   if (!c || !ms) return fail(RT_ERR_INVALID, "null argument");
   if (!c->timed) return fail(RT_ERR_INVALID, c->timing ? "no launch recorded" : "RT_OPT_TIMING is off");
@@ -339,6 +355,11 @@ int rt_ctx_set_option(rt_ctx* c, int32_t option, int32_t value) {
     rt::spec_drop(c);
     c->spec_on = value;
     if (c->uploaded) rt::spec_prepare(c, retry);   // a scene family registered since the upload may hold it
+    return RT_OK;
+  }
+  if (option == RT_OPT_SPEC_SAMPLES) {
+    if (value != 0 && value != 1) return fail(RT_ERR_INVALID, "RT_OPT_SPEC_SAMPLES value %d", value);
+    c->samp_on = value;                  // loaded kernels stay: the points / AA calls just stop (or start) taking them
     return RT_OK;
   }
   if (option == RT_OPT_TILE_MASKS) {

@@ -1931,6 +1931,53 @@ constexpr int rows_lds_doubles() {
               : 0);
 }
 
+// The sample kernels' bodies (the specialised programs rt_spec_points / rt_spec_aa, spec.hip): get_pixel at
+// any (x, y) for rt_render_points_f64 and for the anti-aliasing pass's requested sub-pixels, with the frame
+// storage of the scene's mode exactly as rows_entry takes it for a non-PRIM launch (frames: the one-wave
+// workgroup's s_frames of rows_lds_doubles<MODE, KL_, KP_>() doubles).  No tile masks: a sample is in no tile.
+// Lane i of the launch traces sample i; lanes past n leave before trace(), as in the generic kernels
+// (k_points.hip render_points_kernel, k_views.hip aa_trace_kernel), whose stores these repeat.
+template <int MODE, bool FC, int KL_ = -1, int KP_ = -1>
+__device__ __forceinline__ void points_body(const RtDevScene& S, const double* __restrict__ xy, size_t n, int max_depth,
+                                            double* __restrict__ out, lds_f64* frames) {
+  constexpr bool REFR = MODE != RT_MODE_REFL, CHAIN = MODE == RT_MODE_CHAIN;
+  constexpr int KLR = MODE == RT_MODE_TREE ? RT_LDS_RFRAMES : 0;
+  constexpr int KP = rows_pool_slots<MODE, KL_, KP_>();
+  constexpr int KL = rows_lane_frames<MODE, KL_>();
+  const int lane = threadIdx.x & 63;
+  const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  V3 ro, rd;
+  camera_ray(S.cam, xy[2 * i], xy[2 * i + 1], &ro, &rd);
+  const Col c = trace<REFR, NoRec, KL, FC, KLR, CHAIN, KP>(make_ds(S), ro, rd, max_depth, nullptr, frames + lane, frames,
+                                                         nullptr);
+  out[4 * i] = c.r; out[4 * i + 1] = c.g; out[4 * i + 2] = c.b; out[4 * i + 3] = 1.0;
+}
+// Request i of an anti-aliasing pass: req[2 * i] = the edge pixel's index e, req[2 * i + 1] = sx | sy << 8;
+// edges[e] = x | y << 16; the colour goes to grid point [sx][sy] of pixel e's size x size grid in col
+// (4 doubles per point).  The sample position's operations are the reference's (antialiaser.rs:108-112).
+template <int MODE, bool FC, int KL_ = -1, int KP_ = -1>
+__device__ __forceinline__ void aa_trace_body(const RtDevScene& S, const uint32_t* __restrict__ edges,
+                                              const uint32_t* __restrict__ req, uint32_t n, int size,
+                                              double* __restrict__ col, int max_depth, lds_f64* frames) {
+  constexpr bool REFR = MODE != RT_MODE_REFL, CHAIN = MODE == RT_MODE_CHAIN;
+  constexpr int KLR = MODE == RT_MODE_TREE ? RT_LDS_RFRAMES : 0;
+  constexpr int KP = rows_pool_slots<MODE, KL_, KP_>();
+  constexpr int KL = rows_lane_frames<MODE, KL_>();
+  const int lane = threadIdx.x & 63;
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t e = req[2 * (size_t)i], s = req[2 * (size_t)i + 1];
+  const int x = edges[e] & 0xffff, y = edges[e] >> 16;
+  const int sx = s & 0xff, sy = s >> 8;
+  V3 ro, rd;
+  camera_ray(S.cam, (double)x + ((double)sx / (double)size), (double)y + ((double)sy / (double)size), &ro, &rd);
+  const Col c = trace<REFR, NoRec, KL, FC, KLR, CHAIN, KP>(make_ds(S), ro, rd, max_depth, nullptr, frames + lane, frames,
+                                                         nullptr);
+  double* o = col + ((size_t)e * size * size + sx * size + sy) * 4;
+  o[0] = c.r; o[1] = c.g; o[2] = c.b; o[3] = 1.0;
+}
+
 // The deferred-shadow kernel's body (reflection-only scenes, or refraction chains on request): one
 // wave per 8x8 tile, every tile on the deferred path (trace_deferred), and the costliest tiles split
 // over P = 2, 4 or 8 waves: wave `part` renders pixels [part * 64/P, (part + 1) * 64/P) of the tile

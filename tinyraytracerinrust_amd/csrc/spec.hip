@@ -22,6 +22,9 @@
 //     own, see rtc()), and a code object whose resource use exceeds the known-good bound (VGPRs,
 //     scratch per lane, from the code object's metadata) is refused -- the context then keeps
 //     the generic kernels and rt_ctx_kernel_info says why.  A failed compile never fails an upload.
+//   * the sample programs (rt_spec_points, rt_spec_aa: rt_render_points_f64 and rt_antialias' trace passes,
+//     RT_OPT_SPEC_SAMPLES) are a second job set of a context with the same life, requested by the first such
+//     call after an upload and loaded, refused and reported per path (spec_samples_*, below).
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
 #include <stdio.h>
@@ -276,6 +279,22 @@ static std::string spec_source(const FlatScene& f, const SpecFamily* fam) {
   return s;
 }
 
+// The frame storage the programs' kernels are instantiated with (rows_lds_doubles<MODE, kl, kp>).
+static void spec_frame_layout(int* kl, int* kp) {
+  // stack frames in LDS: 4 waves/SIMD leave 10 KB per one-wave workgroup (the generic kernel's 2
+  // frames at 5 waves: 4 KB); RT_SPEC_LDS_FRAMES (diagnostic builds) overrides the mode's default
+#ifdef RT_SPEC_LDS_FRAMES
+  *kl = RT_SPEC_LDS_FRAMES;
+#else
+  *kl = -1;
+#endif
+  *kp = -1;                                                     // the wave pool's slots (-1: the mode's default)
+#ifdef RT_DIAG_ENV
+  if (const char* e = getenv("RT_SPEC_KL")) *kl = atoi(e);     // diagnostic builds: A/B of the LDS frames
+  if (const char* e = getenv("RT_SPEC_KP")) *kp = atoi(e);
+#endif
+}
+
 // One kernel of the program: rt_spec_rows_<f64><cal> (the megakernel of the scene's mode) or
 // rt_spec_def_<f64><cal> (the deferred-shadow kernel), the generic kernels' exact bodies.
 static std::string spec_kernel(int kind, int mode, bool fc, int f64, int cal) {
@@ -303,18 +322,8 @@ static std::string spec_kernel(int kind, int mode, bool fc, int f64, int cal) {
 #define RT_SPEC_WAVES_PRIM 4
 #endif
   snprintf(waves, sizeof waves, "%d", mode == RT_MODE_CHAIN ? RT_SPEC_WAVES_CHAIN : RT_SPEC_WAVES);
-  // stack frames in LDS: 4 waves/SIMD leave 10 KB per one-wave workgroup (the generic kernel's 2
-  // frames at 5 waves: 4 KB); RT_SPEC_LDS_FRAMES (diagnostic builds) overrides the mode's default
-#ifdef RT_SPEC_LDS_FRAMES
-  int kl = RT_SPEC_LDS_FRAMES;
-#else
-  int kl = -1;
-#endif
-  int kp = -1;                                                  // the wave pool's slots (-1: the mode's default)
-#ifdef RT_DIAG_ENV
-  if (const char* e = getenv("RT_SPEC_KL")) kl = atoi(e);      // diagnostic builds: A/B of the LDS frames
-  if (const char* e = getenv("RT_SPEC_KP")) kp = atoi(e);
-#endif
+  int kl, kp;
+  spec_frame_layout(&kl, &kp);
   if (kind == 4)                                              // a two-eye scene's view megakernel (rt_device.h rows_views_body)
     snprintf(buf, sizeof buf,
              "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(%s))) "
@@ -394,6 +403,36 @@ static std::vector<std::string> spec_programs(const rt_ctx* c, bool with_nm = fa
   for (const SpecKernel& k : spec_kernels(c, with_nm))
     v.push_back((k.kind == 3 || k.kind == 4 ? "#define RT_TILE_MASKS 0\n" : "") + c->spec_src + spec_kernel(k.kind, c->spec_mode, c->spec_fc, k.f64, k.cal));
   return v;
+}
+
+// The sample programs (rt_ctx.h samp_*): rt_spec_points, the specialised kernel of rt_render_points_f64, and
+// rt_spec_aa, the one of rt_antialias' trace passes (rt_device.h points_body / aa_trace_body) -- a second job
+// set of a context, beside the row programs and never among them (spec_kernels / spec_programs above are what
+// rt_scene_precompile, _spec_report and _spec_program name).  One-wave workgroups with the megakernel's
+// occupancy and frame storage; mask-free walks (a sample belongs to no tile), so they compile as kinds 3 and 4.
+static const char* const spec_sample_names[2] = {"rt_spec_points", "rt_spec_aa"};
+static std::string spec_sample_program(const rt_ctx* c, int path) {
+  char buf[1024];
+  int kl, kp;
+  spec_frame_layout(&kl, &kp);
+  const int waves = c->spec_mode == RT_MODE_CHAIN ? RT_SPEC_WAVES_CHAIN : RT_SPEC_WAVES;
+  const char* fc = c->spec_fc ? "true" : "false";
+  if (path == RT_SAMPLE_POINTS)
+    snprintf(buf, sizeof buf,
+             "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(%d))) "
+             "void rt_spec_points(RtDevScene S, const double* __restrict__ xy, size_t n, int max_depth, "
+             "double* __restrict__ out) {\n  __shared__ double s_frames[rows_lds_doubles<%d, %d, %d>()];\n"
+             "  points_body<%d, %s, %d, %d>(S, xy, n, max_depth, out, (lds_f64*)s_frames);\n}\n",
+             waves, c->spec_mode, kl, kp, c->spec_mode, fc, kl, kp);
+  else
+    snprintf(buf, sizeof buf,
+             "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(%d))) "
+             "void rt_spec_aa(RtDevScene S, const uint32_t* __restrict__ edges, const uint32_t* __restrict__ req, "
+             "uint32_t n, int size, double* __restrict__ col, int max_depth) {\n"
+             "  __shared__ double s_frames[rows_lds_doubles<%d, %d, %d>()];\n"
+             "  aa_trace_body<%d, %s, %d, %d>(S, edges, req, n, size, col, max_depth, (lds_f64*)s_frames);\n}\n",
+             waves, c->spec_mode, kl, kp, c->spec_mode, fc, kl, kp);
+  return "#define RT_TILE_MASKS 0\n" + c->spec_src + buf;
 }
 
 // ---- programs: the job table and the compile pool -------------------------------------------------
@@ -631,7 +670,9 @@ int spec_compile(const std::string& src, SpecCode* out, std::string* err) {
 int spec_guard(const SpecCode& c, const std::string& text, std::string* err) {
   const bool def = c.name.rfind("rt_spec_def_", 0) == 0;
   const bool tree = text.find("rows_body<" + std::to_string(RT_MODE_TREE) + ",") != std::string::npos ||
-                    text.find("rows_views_body<" + std::to_string(RT_MODE_TREE) + ",") != std::string::npos;
+                    text.find("rows_views_body<" + std::to_string(RT_MODE_TREE) + ",") != std::string::npos ||
+                    text.find("points_body<" + std::to_string(RT_MODE_TREE) + ",") != std::string::npos ||
+                    text.find("aa_trace_body<" + std::to_string(RT_MODE_TREE) + ",") != std::string::npos;
   const int max_scratch = def ? RT_SPEC_MAX_SCRATCH_DEF : tree ? RT_SPEC_MAX_SCRATCH_TREE : RT_SPEC_MAX_SCRATCH_ROWS;
   if (c.name.empty() || c.vgprs < 0 || c.scratch < 0) {
     *err = "resource guard: the code object's metadata holds no resource usage for the kernel";
@@ -839,7 +880,25 @@ static void spec_text(const FlatScene& f, rt_ctx* c) {
   c->spec_src = spec_source(f, nullptr);
 }
 
+// The sample programs' modules, jobs and reasons (samp_wanted stays: a context that asked keeps asking).
+static void spec_samples_drop(rt_ctx* c) {
+  for (int k = 0; k < 2; ++k) {
+    if (c->samp_mods[k]) (void)hipModuleUnload(c->samp_mods[k]);
+    c->samp_mods[k] = nullptr;
+    c->samp_fn[k] = nullptr;
+    c->samp_jobs[k].reset();                              // drops this context's interest
+    c->samp_error[k].clear();
+    c->samp_res[k].clear();
+    c->samp_cached[k] = false;
+  }
+}
+
+static void spec_rows_drop(rt_ctx* c);
 void spec_drop(rt_ctx* c) {
+  spec_samples_drop(c);
+  spec_rows_drop(c);
+}
+static void spec_rows_drop(rt_ctx* c) {
   for (auto& m : c->spec_mods)
     if (m) (void)hipModuleUnload(m);
   memset(c->spec_mods, 0, sizeof c->spec_mods);
@@ -867,6 +926,108 @@ void spec_prepare(rt_ctx* c, bool retry) {
   }
   if (all_done) c->spec_note = " [process cache]";
   c->spec_t0 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  // a context whose points / AA calls asked for the sample programs before: behind the row programs in the queue
+  if (c->samp_wanted) spec_samples_request(c, retry);
+}
+
+// ---- the sample programs of a context (rt_ctx.h samp_*) --------------------------------------------
+// Why the sample paths of c take no specialised kernel at all ("" where they may).
+static std::string spec_samples_excluded(const rt_ctx* c) {
+  char b[160];
+  if (!c->samp_on) return "RT_OPT_SPEC_SAMPLES is off";
+  if (!c->spec_on) return "RT_OPT_SPECIALIZE is off";
+  if (!c->uploaded || !c->spec_flat) return "no scene uploaded";
+  if (!c->spec_fits) {
+    snprintf(b, sizeof b, "scene too large to specialise: > %d objects or > %d leaves", RT_SPEC_MAX_OBJECTS, RT_SPEC_MAX_LEAVES);
+    return b;
+  }
+  if (c->spec_two_eyes) return "two-eye scene: the view kernels have no specialised sample form";
+  return "";
+}
+
+void spec_samples_request(rt_ctx* c, bool retry) {
+  if (!spec_samples_excluded(c).empty()) return;
+  c->samp_wanted = true;
+  for (int k = 0; k < 2; ++k) {
+    if (c->samp_fn[k] || c->samp_jobs[k]) continue;       // loaded, or on its way
+    if (!c->samp_error[k].empty() && !retry) continue;    // failed for this upload: the path stays generic
+    c->samp_error[k].clear();
+    bool done = false;
+    c->samp_jobs[k] = spec_request(spec_sample_program(c, k), retry, &done);
+    c->samp_cached[k] = done;
+  }
+}
+
+void spec_samples_poll(rt_ctx* c) {
+  for (int k = 0; k < 2; ++k) {
+    std::shared_ptr<SpecJob> j = c->samp_jobs[k];
+    if (!j || !job_finished(j.get())) continue;
+    c->samp_jobs[k].reset();
+    if (j->state.load() != SPEC_DONE) {
+      c->samp_error[k] = j->state.load() == SPEC_CANCELLED ? "compile cancelled (rt_spec_shutdown)" : j->error;
+      continue;
+    }
+    const SpecCode& code = j->code;
+    hipError_t e = hipModuleLoadData(&c->samp_mods[k], code.code.data());
+    if (e == hipSuccess) e = hipModuleGetFunction(&c->samp_fn[k], c->samp_mods[k], spec_sample_names[k]);
+    if (e != hipSuccess) {
+      if (c->samp_mods[k]) (void)hipModuleUnload(c->samp_mods[k]);
+      c->samp_mods[k] = nullptr;
+      c->samp_fn[k] = nullptr;
+      c->samp_error[k] = std::string("loading the specialised code object failed: ") + hipGetErrorString(e);
+      continue;
+    }
+    char b[256];
+    snprintf(b, sizeof b, "%s of hipRTC %016llx, %d VGPRs (%d spilled), %d B/lane scratch, compiled in %.0f ms%s",
+             spec_sample_names[k], (unsigned long long)fnv1a(c->spec_src), code.vgprs, code.vspill, code.scratch, code.compile_ms,
+             c->samp_cached[k] ? " [process cache]" : code.from_disk ? " [disk cache]" : "");
+    c->samp_res[k] = b;
+  }
+}
+
+int spec_samples_wait(rt_ctx* c, double timeout_ms) {
+  spec_samples_request(c);
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int k = 0; k < 2; ++k) {
+    if (!c->samp_jobs[k]) continue;
+    double left = -1.0;
+    if (timeout_ms >= 0)
+      left = std::max(0.0, timeout_ms - std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (!job_wait(c->samp_jobs[k].get(), left)) return RT_PENDING;
+  }
+  spec_samples_poll(c);
+  return RT_OK;
+}
+
+hipFunction_t spec_sample_kernel(rt_ctx* c, int path) {
+  static const char* const generic[2] = {"points", "aa trace"};
+  static const char* const specialised[2] = {"points (specialised)", "aa trace (specialised)"};
+  c->last_sample = generic[path];
+  if (!spec_samples_excluded(c).empty()) return nullptr;
+  spec_samples_request(c);
+  spec_samples_poll(c);
+  // the program's clamp form is the scene's; RT_OPT_FAST_CLAMP 0 on a min/max-clamp scene keeps the generic kernel
+  if ((c->dev.colour_fast != 0 && c->fast_clamp) != c->spec_fc) return nullptr;
+  if (c->samp_fn[path]) c->last_sample = specialised[path];
+  return c->samp_fn[path];
+}
+
+std::string spec_sample_info(rt_ctx* c) {
+  static const char* const label[2] = {"points", "aa trace"};
+  const std::string excluded = spec_samples_excluded(c);
+  std::string s;
+  for (int k = 0; k < 2; ++k) {
+    s += std::string(k ? "; " : "") + label[k] + ": ";
+    if (!excluded.empty()) s += "generic (" + excluded + ")";
+    else if (c->samp_fn[k] && (c->dev.colour_fast != 0 && c->fast_clamp) != c->spec_fc)
+      s += "generic (RT_OPT_FAST_CLAMP is off and the program clamps with min/max)";
+    else if (c->samp_fn[k]) s += "specialised (" + c->samp_res[k] + ")";
+    else if (c->samp_jobs[k]) s += "generic (the specialised kernel is compiling in the background)";
+    else if (!c->samp_error[k].empty()) s += "generic (specialisation failed: " + c->samp_error[k] + ")";
+    else s += "generic (not requested yet: no points or anti-aliasing call since the upload)";
+  }
+  s += std::string("; last sample launch: ") + c->last_sample;
+  return s;
 }
 
 int spec_poll(rt_ctx* c) {
@@ -896,8 +1057,8 @@ int spec_poll(rt_ctx* c) {
     }
     if (e != hipSuccess) {
       c->spec_jobs.clear();
-      spec_drop(c);
-      c->spec_error = std::string("loading the specialised code object failed: ") + hipGetErrorString(e);
+      spec_rows_drop(c);                                    // the sample programs are a job set of their own
+      c->spec_error =std::string("loading the specialised code object failed: ") + hipGetErrorString(e);
       return RT_OK;
     }
     ms = std::max(ms, code.compile_ms);
@@ -984,6 +1145,15 @@ extern "C" int rt_scene_precompile(const rt_scene* s, double* compile_ms) {
   return rc;
 }
 
+// One kernel's line of rt_scene_spec_report / rt_scene_sample_report.
+static std::string report_line(const SpecCode& c) {
+  char line[512];
+  snprintf(line, sizeof line, "%s: vgprs %d spilled %d sgprs %d scratch %d occupancy %d code %zu compile_ms %.0f source %s\n",
+           c.name.c_str(), c.vgprs, c.vspill, c.sgprs, c.scratch, c.occupancy, c.code.size(), c.compile_ms,
+           c.from_disk ? "disk" : "hiprtc");
+  return line;
+}
+
 // rt_scene_spec_report (include/rt_abi.h): compile (or find) the scene's level-1 programs and describe
 // them: the compiler, and per kernel its resource use and how it was obtained
 extern "C" int rt_scene_spec_report(const rt_scene* s, char* buf, size_t cap, size_t* len) {
@@ -997,14 +1167,41 @@ extern "C" int rt_scene_spec_report(const rt_scene* s, char* buf, size_t cap, si
   if (rc) return rc;
   // source: how the code object was made -- by hipRTC in this process, or read from the disk cache
   std::string text = "compiler: " + rtc().identity + (rtc().rocm ? " (the ROCm installation's hipRTC)" : "") + "\n";
-  for (size_t i = 0; i < jobs.size(); ++i) {
-    const SpecCode& c = jobs[i]->code;
-    char line[512];
-    snprintf(line, sizeof line, "%s: vgprs %d spilled %d sgprs %d scratch %d occupancy %d code %zu compile_ms %.0f source %s\n",
-             c.name.c_str(), c.vgprs, c.vspill, c.sgprs, c.scratch, c.occupancy, c.code.size(), c.compile_ms,
-             c.from_disk ? "disk" : "hiprtc");
-    text += line;
+  for (size_t i = 0; i < jobs.size(); ++i) text += report_line(jobs[i]->code);
+  *len = text.size();
+  if (cap > 0) {
+    const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;
+    memcpy(buf, text.data(), n);
+    buf[n] = 0;
   }
+  return RT_OK;
+}
+
+// rt_scene_sample_report (include/rt_abi.h): compile (or find) the scene's two sample programs, no device
+// needed, and describe them, one line per kernel in rt_scene_spec_report's format
+extern "C" int rt_scene_sample_report(const rt_scene* s, char* buf, size_t cap, size_t* len) {
+  if (!s || !len || (cap > 0 && !buf)) return fail(RT_ERR_INVALID, "null argument");
+  rt::FlatScene f;
+  int rc = rt::flatten(*s, &f);
+  if (rc) return rc;
+  rt_ctx tmp;
+  rt::spec_text(f, &tmp);
+  if (!tmp.spec_fits)
+    return fail(RT_ERR_UNSUPPORTED, "scene of %zu objects / %zu leaves is not specialised (limits %d / %d)",
+                f.objects.size(), f.leaves.size(), RT_SPEC_MAX_OBJECTS, RT_SPEC_MAX_LEAVES);
+  if (tmp.spec_two_eyes) return fail(RT_ERR_UNSUPPORTED, "a two-eye scene has no specialised sample kernels");
+  std::vector<std::shared_ptr<SpecJob>> jobs;
+  std::vector<bool> done;
+  for (int k = 0; k < 2; ++k) {
+    bool d = false;
+    jobs.push_back(spec_request(rt::spec_sample_program(&tmp, k), false, &d));
+    done.push_back(d);
+  }
+  double ms = 0.0;
+  rc = wait_all(jobs, done, &ms);
+  if (rc) return rc;
+  std::string text;
+  for (size_t i = 0; i < jobs.size(); ++i) text += report_line(jobs[i]->code);
   *len = text.size();
   if (cap > 0) {
     const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;

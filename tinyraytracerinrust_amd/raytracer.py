@@ -205,6 +205,16 @@ class Scene:
         check(lib().rt_scene_spec_report(self.h, buf, n.value + 1, ctypes.byref(n)))
         return buf.value.decode()
 
+    def sample_report(self) -> str:
+        """rt_scene_sample_report: compile (or find) the scene's two sample programs (rt_spec_points,
+        rt_spec_aa: the specialised kernels of render_points and of the anti-aliasing trace) and describe
+        them, one line per kernel in spec_report's format."""
+        n = ctypes.c_size_t()
+        check(lib().rt_scene_sample_report(self.h, None, 0, ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(n.value + 1)
+        check(lib().rt_scene_sample_report(self.h, buf, n.value + 1, ctypes.byref(n)))
+        return buf.value.decode()
+
     @staticmethod
     def register_family(scenes) -> float:
         """rt_spec_family_register: one specialised program for scenes of the same structure (the
@@ -463,6 +473,25 @@ class Renderer:
         ``timeout_ms`` passed (False); raises RtError when the compile failed or the guard refused it."""
         rc = check(lib().rt_ctx_spec_wait(self.h, int(timeout_ms)))
         return rc != _lib.RT_PENDING
+
+    def set_spec_samples(self, on: bool) -> None:
+        """rt_ctx_set_option(RT_OPT_SPEC_SAMPLES): let render_points and the anti-aliasing trace take the
+        scene's specialised sample kernels once they are loaded (default), or always the generic ones
+        (same samples)."""
+        check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_SPEC_SAMPLES, 1 if on else 0))
+
+    def spec_wait_samples(self, timeout_ms: int = -1) -> bool:
+        """rt_ctx_spec_wait_samples: request the sample programs if this renderer has not yet, and block
+        until they are loaded (True) or ``timeout_ms`` passed (False); raises RtError when one failed."""
+        rc = check(lib().rt_ctx_spec_wait_samples(self.h, int(timeout_ms)))
+        return rc != _lib.RT_PENDING
+
+    def sample_kernel_info(self) -> str:
+        """rt_ctx_sample_kernel_info: per sample path (points, aa trace) generic (and why) or specialised
+        (and its resources), and what the last points / anti-aliasing trace launch ran."""
+        buf = ctypes.create_string_buffer(4096)
+        check(lib().rt_ctx_sample_kernel_info(self.h, buf, 4096))
+        return buf.value.decode()
 
     def kernel_info(self) -> str:
         """rt_ctx_kernel_info: generic or scene-specialised kernels, and what the last row launch ran."""
