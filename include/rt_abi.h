@@ -324,6 +324,12 @@ int rt_ctx_synchronize(rt_ctx* ctx);
  * (costliest tile <= the work per wave slot; launches without a measured order take none); 2 every launch
  * that can; 0 none (the mask-free kernels: the walks of a library without masks).  Same pixels.
  * rt_ctx_kernel_info says whether the last launch took masks.
+ * RT_OPT_TILE_RECORDS: 1 (default) a launch that takes masks reads them from dispatch records -- one 32-byte
+ * record per entry of the launch's tile order holding the tile's first column, first output row and mask
+ * words, gathered on the device (on the launch's stream, no host synchronisation) whenever the masks or the
+ * order are new -- so a wave's prologue is one scalar load where the order entry, the tile division and the
+ * mask words were dependent trips; 0: the kernels read the order and the tile-indexed mask table themselves.
+ * Same pixels.  rt_ctx_kernel_info says "; tile records: on / off" for the last launch.
  * Two-eye scenes (rt_scene_set_camera_kind) always take the view megakernels (k_stereo.hip: one launch over
  * the tiles of both eyes, mask-free walks): RT_KERNEL_DEFERRED, RT_KERNEL_WAVEFRONT and RT_OPT_TILE_MASKS have
  * no effect on them; RT_OPT_TILE_ORDER and RT_OPT_SPECIALIZE apply (rt_ctx_kernel_info says which kernel ran).
@@ -339,7 +345,8 @@ int rt_ctx_synchronize(rt_ctx* ctx);
  * Option 7 is retired (round 4's tail kernel, measured slower than the launch it shortened). */
 typedef enum rt_option {
   RT_OPT_KERNEL = 0, RT_OPT_TIMING = 1, RT_OPT_TILE_ORDER = 2, RT_OPT_FAST_CLAMP = 3, RT_OPT_WAVEFRONT_CAP = 4,
-  RT_OPT_WAVEFRONT_PAIRS = 5, RT_OPT_SPECIALIZE = 6, RT_OPT_TILE_MASKS = 8, RT_OPT_SPEC_SAMPLES = 9
+  RT_OPT_WAVEFRONT_PAIRS = 5, RT_OPT_SPECIALIZE = 6, RT_OPT_TILE_MASKS = 8, RT_OPT_SPEC_SAMPLES = 9,
+  RT_OPT_TILE_RECORDS = 10
 } rt_option;
 typedef enum rt_kernel_choice {
   RT_KERNEL_AUTO = 0, RT_KERNEL_MEGA = 1, RT_KERNEL_DEFERRED = 2, RT_KERNEL_WAVEFRONT = 3

@@ -27,6 +27,22 @@ __global__ __launch_bounds__(64) void tile_masks_kernel(const RtTileMaskScene* _
   for (int k = 0; k < RT_TILEMASK_WORDS; ++k) out[(size_t)tile * RT_TILEMASK_WORDS + k] = w[k];
 }
 
+// The dispatch records of a launch (rt_blob.h RtTileRec): one thread per order entry gathers the entry's tile
+// (order[e], or e without an order) from the tile-indexed mask table.
+__global__ __launch_bounds__(64) void tile_records_kernel(const uint32_t* __restrict__ masks, const int32_t* __restrict__ order,
+                                                          uint32_t n_entries, uint32_t n_tiles, uint32_t tiles_x,
+                                                          RtTileRec* __restrict__ out) {
+  const uint32_t e = blockIdx.x * 64u + threadIdx.x;
+  if (e >= n_entries) return;
+  const uint32_t tile = order ? (uint32_t)order[e] : e;
+  RtTileRec r;
+  r.x0 = (int32_t)((tile % tiles_x) * RT_TILE_W);
+  r.r0 = (int32_t)((tile / tiles_x) * (64 / RT_TILE_W));
+  for (int k = 0; k < RT_TILEMASK_WORDS; ++k)
+    r.mask[k] = tile < n_tiles ? masks[(size_t)tile * RT_TILEMASK_WORDS + k] : 0xffffffffu;
+  out[e] = r;
+}
+
 bool finite3(const double* p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
 
 // What the predicate reads of a flattened scene.  valid = 0 (every word all ones) for scenes of more than
@@ -83,6 +99,12 @@ void drop_mask(rt_ctx::MaskSlot& s) {
   s = rt_ctx::MaskSlot();
 }
 
+void drop_rec(rt_ctx::RecSlot& s) {
+  if (s.d_recs) (void)hipFree(s.d_recs);         // hipFree waits for work that may still read it
+  if (s.ready) (void)hipEventDestroy(s.ready);
+  s = rt_ctx::RecSlot();
+}
+
 // Geometry of a band launch as launch_bands computes it
 int mask_geometry(int width, int height, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
                   int* n_rows, size_t* n_tiles) {
@@ -119,6 +141,7 @@ int mask_slot(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t 
     RT_HIP(hipGetLastError());
     RT_HIP(hipEventRecord(slot->ready, st));
     slot->fill_stream = st;
+    slot->fill_id = ++c->mask_fills;
     slot->valid = true;
   }
   slot->last_use = ++c->use_clock;
@@ -140,6 +163,11 @@ namespace rt {
 
 void drop_masks(rt_ctx* c) {
   for (auto& s : c->masks) drop_mask(s);
+  drop_records(c);                     // gathered from them
+}
+
+void drop_records(rt_ctx* c) {
+  for (auto& s : c->recs) drop_rec(s);
 }
 
 // The mask plane: the first object in draw order that is one plane leaf whose constant unit normal the
@@ -164,14 +192,61 @@ size_t put_mask_scene(const FlatScene& f, std::vector<uint8_t>& blob, bool* ok) 
   return off;
 }
 
-int launch_masks(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t n_tiles, const uint32_t** table) {
+int launch_masks(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t n_tiles, const uint32_t** table,
+                 const void** mslot) {
   *table = nullptr;
+  if (mslot) *mslot = nullptr;
   if (!c->tile_masks || !c->masks_ok) return RT_OK;
   static const bool off = diag_env("RT_NO_TILE_MASKS");
   if (off) return RT_OK;
   rt_ctx::MaskSlot* slot = nullptr;
   RT_TRY(mask_slot(c, st, a0, a1, a2, a3, n_tiles, &slot));
   *table = slot->d_masks;
+  if (mslot) *mslot = slot;
+  return RT_OK;
+}
+
+// The record table of a masked launch: found by the mask fill it read and the calibration that wrote its order
+// (a table of an earlier fill -- the masks are dropped on every upload -- or of another order is never taken),
+// else gathered on st, behind the mask fill: launch_masks has put the fill, or a wait for its event, on st
+// already.  Launches on other streams wait for the gather's own event.
+int launch_records(rt_ctx* c, hipStream_t st, const void* mask_slot, const int32_t* d_order, uint64_t order_id,
+                   uint32_t n_entries, const RtTileRec** table) {
+  const rt_ctx::MaskSlot* ms = (const rt_ctx::MaskSlot*)mask_slot;
+  *table = nullptr;
+  rt_ctx::RecSlot* slot = nullptr;
+  for (auto& s : c->recs)
+    if (s.valid && s.fill_id == ms->fill_id && s.order_id == order_id && s.n_entries == n_entries) slot = &s;
+  if (!slot) {
+    slot = &c->recs[0];
+    for (auto& s : c->recs) {
+      if (!s.valid) { slot = &s; break; }
+      if (s.last_use < slot->last_use) slot = &s;
+    }
+    drop_rec(*slot);
+    RT_HIP(hipMalloc((void**)&slot->d_recs, (size_t)n_entries * sizeof(RtTileRec)));
+    RT_HIP(hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming));
+    slot->order_id = order_id;
+    slot->fill_id = ms->fill_id;
+    slot->n_entries = n_entries;
+    const uint32_t tiles_x = (uint32_t)((c->dev.width + RT_TILE_W - 1) / RT_TILE_W);
+    hipLaunchKernelGGL(tile_records_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, st, (const uint32_t*)ms->d_masks, d_order,
+                       n_entries, (uint32_t)ms->n_tiles, tiles_x, slot->d_recs);
+    RT_HIP(hipGetLastError());
+    RT_HIP(hipEventRecord(slot->ready, st));
+    slot->fill_stream = st;
+    slot->valid = true;
+  }
+  slot->last_use = ++c->use_clock;
+  if (!slot->seen_ready && slot->fill_stream != st) {      // another stream's launch: after the gather
+    if (hipEventQuery(slot->ready) == hipSuccess) {
+      slot->seen_ready = true;
+    } else {
+      (void)hipGetLastError();
+      RT_HIP(hipStreamWaitEvent(st, slot->ready, 0));
+    }
+  }
+  *table = slot->d_recs;
   return RT_OK;
 }
 

@@ -117,6 +117,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   hipStream_t st = (hipStream_t)stream;   // NULL = the device's default stream
   (void)spec_poll(c);                     // the scene-specialised kernels, once their background compile is done
   c->last_masked = false;
+  c->last_records = false;
   const bool dev_out = is_device_ptr(out);
   uint8_t* target = (uint8_t*)out;
   size_t tstride = stride;
@@ -182,6 +183,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
       memcpy(slot->key, key, sizeof(key));
       slot->n_tiles = n_tiles;
       slot->grid = (uint32_t)n_tiles;
+      slot->order_id = ++c->order_ids;
       calibrate = true;
     }
     slot->last_use = ++c->use_clock;
@@ -201,6 +203,8 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   // A table that is new since the upload is filled here, AHEAD of the timing event: rt_ctx_last_kernel_ms
   // reports the render kernel alone.  (The kernel choice below is restated for it.)
   const uint32_t* mask_table = nullptr;
+  const void* mask_slot = nullptr;
+  const RtTileRec* rec_table = nullptr;       // the launch's dispatch records (RT_OPT_TILE_RECORDS), gathered from both
   if (c->spec_mod && !refr && c->spec_mode == RT_MODE_REFL && !c->spec_family && c->dev.n_objects <= 32 &&
       (c->dev.colour_fast != 0 && c->fast_clamp) == c->spec_fc) {
     // RT_OPT_TILE_MASKS 1: the primary-ray kernel always takes the table (its one walk per pixel only gains);
@@ -209,7 +213,10 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
     const bool prim0 = max_depth == 0 && dmode != 1 && c->spec_prim[f64 ? 1 : 0][calibrate ? 1 : 0];
     const bool want = c->tile_masks == 2 || (c->tile_masks == 1 && (prim0 || (order && slot->masks_pay)));
     if (want && (prim0 || (!deferred && c->spec_rows[f64 ? 1 : 0][calibrate ? 1 : 0])))
-      RT_TRY(launch_masks(c, st, a0, a1, a2, a3, n_tiles, &mask_table));
+      RT_TRY(launch_masks(c, st, a0, a1, a2, a3, n_tiles, &mask_table, &mask_slot));
+    // (a deferred slot's entries carry split parts: no plain tiles to gather)
+    if (mask_table && c->tile_records && !(order && slot->deferred))
+      RT_TRY(launch_records(c, st, mask_slot, order, order ? slot->order_id : 0, grid.x, &rec_table));
   }
   if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
   // the row kernels carry the context's completion event for this stream as their stop event
@@ -283,12 +290,15 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
     return fail(RT_ERR_UNSUPPORTED, "a pooled kernel for a scene of %d objects (one-byte object index)", c->dev.n_objects);
   const uint32_t* masks = sfn && !deferred && mode == RT_MODE_REFL ? mask_table : nullptr;
   c->last_masked = masks != nullptr;
+  const RtTileRec* recs = masks ? rec_table : nullptr;
+  c->last_records = recs != nullptr;
   // a megakernel launch without a table runs the program's mask-free megakernel (spec.hip kind 3)
   if (sfn && !prim && !deferred && !masks && c->spec_rows_nm[f64 ? 1 : 0][calibrate ? 1 : 0])
     sfn = c->spec_rows_nm[f64 ? 1 : 0][calibrate ? 1 : 0];
   if (sfn) {
     void* kargs[] = {&c->dev, (void*)&a0, (void*)&a1, (void*)&a2, (void*)&a3, &max_depth, &target, &tstride,
-                     (void*)&order, &cost, (void*)&rgbi, (void*)&masks};
+                     (void*)&order, &cost, (void*)&rgbi, (void*)&masks, (void*)&recs};   // (a kernel reads as
+    // many as it declares: the masked single-scene kernels take the records, spec.hip)
     // hipExtModuleLaunchKernel takes the global work size in work-items (grid x 64)
     RT_HIP(hipExtModuleLaunchKernel(sfn, grid.x * 64u, 1, 1, 64, 1, 1, 0, st, kargs, nullptr, nullptr, mev, 0));
   }

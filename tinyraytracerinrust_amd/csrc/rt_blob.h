@@ -46,6 +46,16 @@ using __hip_internal::uint64_t;
 #endif
 // Per-tile object masks (rt_tilemask.h): words per tile -- prim, shadow[0..3], refl; bit o = object o.
 #define RT_TILEMASK_WORDS 6
+// Dispatch record of one order entry of a masked launch (k_masks.hip tile_records_kernel; rt_device.h
+// rows_entry reads it with one 32-byte scalar load): the entry's tile as its first column and first output
+// row (no division in the kernel) and the tile's mask words.  A calibrating launch has no order: its entry e
+// is tile e, so the record holds no tile index.  Entry e's record is records[e]: four consecutive workgroups
+// share a 128-byte line.  (A layout that gives each XCD's workgroups -- e, e + 8, ... -- a contiguous run was
+// measured equal, DESIGN.md section 7, and cost the kernel an argument and a multiply.)
+struct alignas(32) RtTileRec {
+  int32_t x0, r0;                   // the tile's first column and first output row
+  uint32_t mask[RT_TILEMASK_WORDS];
+};
 #define RT_MODE_REFL 0
 #define RT_MODE_CHAIN 1
 #define RT_MODE_TREE 2

@@ -65,6 +65,7 @@ struct rt_ctx {
     bool masks_pay = false;           // the calibration found the launch throughput-bound: the masked megakernel
                                       // (RT_OPT_TILE_MASKS 1); kept with the order across same-structure uploads
     bool valid = false;               // set once the sorted order is on the device
+    uint64_t order_id = 0;            // which calibration of the context wrote d_order (RecSlot; never 0)
   };
   static constexpr int RT_ORDER_SLOTS = 8;
   OrderSlot order[RT_ORDER_SLOTS];
@@ -84,11 +85,37 @@ struct rt_ctx {
     uint64_t last_use = 0;
     hipStream_t fill_stream = nullptr;
     hipEvent_t ready = nullptr;
+    uint64_t fill_id = 0;             // which fill of the context this table is (RecSlot)
     bool seen_ready = false;
     bool valid = false;
   };
   static constexpr int RT_MASK_SLOTS = 8;
   MaskSlot masks[RT_MASK_SLOTS];
+  // Dispatch records (rt_blob.h RtTileRec, k_masks.hip): per order entry of a masked launch the tile's first
+  // column, first output row and mask words, gathered on the device from the geometry's mask table and the
+  // launch's tile order (null: the identity) -- one scalar load in the kernel where the order, the tile
+  // division and the mask words were dependent trips.  A table is keyed by its two inputs, each named by a
+  // number the context never reuses: the mask fill it read (MaskSlot::fill_id -- masks are dropped on every
+  // upload and filled again) and the calibration that wrote its order (OrderSlot::order_id, 0: no order).  A
+  // table of an earlier fill or order is therefore never found again; its successor is gathered on the
+  // launch's stream, behind the mask fill, with no host synchronisation.  Launches on other streams wait for
+  // `ready` as they do for the masks'.  Same LRU and free rules as the mask tables.
+  struct RecSlot {
+    uint64_t order_id = 0;            // the order gathered from (0: the identity)
+    uint64_t fill_id = 0;             // the mask fill gathered from
+    RtTileRec* d_recs = nullptr;
+    uint32_t n_entries = 0;           // order entries = records
+    uint64_t last_use = 0;
+    hipStream_t fill_stream = nullptr;
+    hipEvent_t ready = nullptr;
+    bool seen_ready = false;
+    bool valid = false;
+  };
+  static constexpr int RT_REC_SLOTS = 8;
+  RecSlot recs[RT_REC_SLOTS];
+  uint64_t mask_fills = 0, order_ids = 0;   // count mask fills and calibrations: MaskSlot::fill_id, OrderSlot::order_id
+  bool tile_records = true;             // rt_ctx_set_option(RT_OPT_TILE_RECORDS)
+  bool last_records = false;            // the last row launch passed a record table (rt_ctx_kernel_info)
   int tile_masks = 1;                   // rt_ctx_set_option(RT_OPT_TILE_MASKS): 0 never, 1 where they pay (OrderSlot::masks_pay), 2 always
   bool masks_ok = false;                // the uploaded scene has a mask scene in its blob (<= 32 objects)
   const void* d_mask_scene = nullptr;   // RtTileMaskScene in the blob
@@ -177,7 +204,14 @@ void drop_masks(rt_ctx* c);                    // every table (upload, free): hi
 int tilemask_plane(const FlatScene& f);        // the mask plane's object index, -1: none
 // The table of the geometry (a0..a3 as launch_wavefront) for a launch on st, filled on st first if it is new
 // since the upload; *table = nullptr when the context takes no masks.
-int launch_masks(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t n_tiles, const uint32_t** table);
+// (*mslot: the table's slot, for launch_records)
+int launch_masks(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t n_tiles, const uint32_t** table,
+                 const void** mslot = nullptr);
+// The dispatch records (RecSlot) of a launch of n_entries order entries (d_order of calibration order_id; null and
+// 0: the identity) whose mask table is mask_slot's, gathered on st first if the masks or the order are new.
+int launch_records(rt_ctx* c, hipStream_t st, const void* mask_slot, const int32_t* d_order, uint64_t order_id,
+                   uint32_t n_entries, const RtTileRec** table);
+void drop_records(rt_ctx* c);                  // every record table (upload, free)
 size_t put_mask_scene(const FlatScene& f, std::vector<uint8_t>& blob, bool* ok);   // appends the RtTileMaskScene
 int ensure_scratch(rt_ctx* c, size_t bytes);   // grow-only device scratch for host-pointer launches
 bool is_device_ptr(const void* p);

@@ -300,6 +300,7 @@ int rt_ctx_kernel_info(rt_ctx* c, char* buf, size_t cap) {
   }
   s += std::string("; last launch: ") + c->last_kernel;
   s += c->last_masked ? "; tile masks: on" : "; tile masks: off";
+  s += c->last_records ? "; tile records: on" : "; tile records: off";
   snprintf(buf, cap, "%s", s.c_str());
   return RT_OK;
 }
@@ -365,6 +366,11 @@ int rt_ctx_set_option(rt_ctx* c, int32_t option, int32_t value) {
   if (option == RT_OPT_TILE_MASKS) {
     if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "RT_OPT_TILE_MASKS value %d", value);
     c->tile_masks = value;               // the tables stay: launches just stop (or start) passing them
+    return RT_OK;
+  }
+  if (option == RT_OPT_TILE_RECORDS) {
+    if (value != 0 && value != 1) return fail(RT_ERR_INVALID, "RT_OPT_TILE_RECORDS value %d", value);
+    c->tile_records = value != 0;        // the tables stay: launches just stop (or start) passing them
     return RT_OK;
   }
   if (option == RT_OPT_WAVEFRONT_PAIRS) {

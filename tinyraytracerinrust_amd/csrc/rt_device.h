@@ -725,6 +725,15 @@ __device__ __forceinline__ void spec_for(F&& f) {
 #define RT_TILE_MASKS 1
 #endif
 #endif
+// The dispatch-record operands of the masked single-scene kernels (spec.hip writes them into the megakernel's
+// and the primary-ray kernel's text; rows_entry below): a program without masks declares none.
+#if RT_TILE_MASKS
+#define RT_REC_PARAMS , const RtTileRec* __restrict__ recs
+#define RT_REC_ARGS , recs
+#else
+#define RT_REC_PARAMS
+#define RT_REC_ARGS
+#endif
 template <bool SORD> constexpr uint32_t spec_boxed_bits(int b, int e) {     // the boxed objects of nodes [b, e)
   uint32_t m = 0;
   for (int i = b; i < e; ++i) {
@@ -1220,6 +1229,15 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t m) {                 // s
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
+// A wave's tile-mask words (rt_tilemask.h) as trace() takes them: wave-uniform values the caller read with
+// the wave's dispatch record (rows_entry), scalar registers for the whole trace; all ones without a table.
+struct TileMask { uint32_t w[RT_TILEMASK_WORDS]; };
+__device__ __forceinline__ TileMask tile_mask_ones() {
+  TileMask m;
+  for (int k = 0; k < RT_TILEMASK_WORDS; ++k) m.w[k] = 0xffffffffu;
+  return m;
+}
+
 // get_ray_color (raytracer.rs:132-287) for one primary ray, recursion unrolled onto a per-lane
 // frame stack.  REFR = the scene has a transparent object (refraction frames need more state).
 // KL > 0: frames 0..KL-1 of the stack are in LDS at lf[(f * 4 + c) * 64] (lf = this lane's slot);
@@ -1230,10 +1248,11 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t m) {                 // s
 // frame never carries a pending reflection: frames are (A, w) as in the reflection-only kernels.
 template <bool REFR, class Rec = NoRec, int KL = 0, bool FC = false, int KLR = 0, bool CHAIN = false, int KP = 0>
 RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, lds_f64* lf = nullptr,
-                lds_f64* lp = nullptr, const uint32_t* tmask_ = nullptr) {
-  // Tile masks (rt_tilemask.h): the wave's RT_TILEMASK_WORDS words, read with scalar loads where a walk
-  // takes one.  Reflection-only kernels: every hit spawns at most one ray and a lane that spawns none
-  // leaves the loop, so iteration k traces the depth-k rays of the lanes still here.  The depth-0
+                lds_f64* lp = nullptr, const TileMask tm = tile_mask_ones()) {
+  // Tile masks (rt_tilemask.h): the wave's RT_TILEMASK_WORDS words, scalars (all ones without a table; a
+  // second form of this function that also kept the table's lazy scalar loads behind a wave-uniform branch
+  // gave back 1.6 % of the 4K frame).  Reflection-only kernels: every hit spawns at most
+  // one ray and a lane that spawns none leaves the loop, so iteration k traces the depth-k rays of the lanes still here.  The depth-0
   // nearest hit takes `prim`; where every lane that hit something hit the mask plane (one ballot, kept
   // in a scalar), light l's depth-0 shadow walk takes shadow[l] and the depth-1 nearest hit `refl`;
   // every other walk takes all ones.  One walk either way: the mask is an operand, not a second copy.
@@ -1244,10 +1263,6 @@ RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, ld
   constexpr bool MASKS = false;
   constexpr int mask_plane = -1;
 #endif
-  const cptr<uint32_t> tmask = as_const(tmask_);
-  auto mask_word = [&](int k) -> uint32_t {
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)tmask[k]);
-  };
   [[maybe_unused]] bool plane_tile = false;   // depth 0: every hit of the wave is on the mask plane
   double fA[RT_MAX_DEPTH_CAP][3];     // parent colour already intensified by (1 - w)
   double fW[RT_MAX_DEPTH_CAP];        // child weight w (transparency or reflectivity)
@@ -1347,8 +1362,8 @@ RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, ld
       // their first active lane's copies, which keeps the mask (and every test on it) scalar.
       const int it = __builtin_amdgcn_readfirstlane(iter);
       const bool pt = __builtin_amdgcn_readfirstlane((int)plane_tile) != 0;
-      if (tmask_ && it == 0) nmask = mask_word(0);
-      else if (pt && it == 1) nmask = mask_word(5);
+      if (it == 0) nmask = tm.w[0];
+      else if (pt && it == 1) nmask = tm.w[5];
       nmask = (uint32_t)__builtin_amdgcn_readfirstlane((int)nmask);
     }
     oi = nearest_hit<SHARE, OBB>(S, ro, rd, &t_hit, nmask);
@@ -1358,7 +1373,7 @@ RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, ld
     // no lane re-enters -- the bounce loop never restarts a pixel.  A change that lets a lane take a second
     // primary ray inside this loop must clear plane_tile with it.)
     if constexpr (MASKS)
-      if (iter == 0) plane_tile = tmask_ && mask_plane >= 0 && __ballot(oi >= 0 && oi != mask_plane) == 0;
+      if (iter == 0) plane_tile = mask_plane >= 0 && __ballot(oi >= 0 && oi != mask_plane) == 0;
     const V3 p = add(ro, scale(rd, t_hit));                               // :162
     if constexpr (RECORD) slot = rec->begin(depth, ray_type, ro, rd, t_hit, oi, p);
     V3 nrm = {0.0, 0.0, 0.0};
@@ -1383,7 +1398,12 @@ RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, ld
         double t;                                                          // :176-197
         uint32_t smask = 0xffffffffu;
         if constexpr (MASKS)
-          if (__builtin_amdgcn_readfirstlane((int)(plane_tile && iter == 0)) != 0 && k < 4) smask = mask_word(1 + k);
+          if (__builtin_amdgcn_readfirstlane((int)(plane_tile && iter == 0)) != 0 && k < 4) {
+            // (k is the same in every lane, but the loop sits in the branch of the lanes that hit: the word is
+            // chosen by its first-lane copy, scalar selects)
+            const int ks = __builtin_amdgcn_readfirstlane(k);
+            smask = ks == 0 ? tm.w[1] : ks == 1 ? tm.w[2] : ks == 2 ? tm.w[3] : tm.w[4];
+          }
         t = shadow_transparency<SHARE, OBB>(S, p, sdir, ll, smask);
         if (!have_shading) {
           shade_inputs(S, oi, p, &nrm, &c, &transp, &refl, &nlen);
@@ -1834,28 +1854,55 @@ template <int MODE, bool F64, bool CAL, bool FC, int KL_ = -1, int KP_ = -1, boo
 __device__ __forceinline__ void rows_entry(const RtDevScene& S, unsigned entry, int y_first, int band_rows, int band_pitch,
                                            int n_rows, int max_depth, uint8_t* __restrict__ out, size_t stride,
                                            const int32_t* __restrict__ order, uint32_t* __restrict__ cost, int rgb,
-                                           lds_f64* frames, const uint32_t* __restrict__ masks = nullptr) {
+                                           lds_f64* frames, const uint32_t* __restrict__ masks = nullptr,
+                                           const RtTileRec* __restrict__ recs = nullptr) {
   constexpr bool REFR = MODE != RT_MODE_REFL, CHAIN = MODE == RT_MODE_CHAIN;
   constexpr int KLR = PRIM ? 0 : MODE == RT_MODE_TREE ? RT_LDS_RFRAMES : 0;
   constexpr int KP = PRIM ? 0 : rows_pool_slots<MODE, KL_, KP_>();
   constexpr int KL = PRIM ? 0 : rows_lane_frames<MODE, KL_>();
   if constexpr (PRIM) max_depth = 0;
   const int lane = threadIdx.x & 63;
-  const unsigned tile = CAL || !order ? entry : (unsigned)order[entry];
   [[maybe_unused]] uint64_t t_start = 0;
   if constexpr (CAL) t_start = wall_clock64();
+#if defined(RT_SPEC) && RT_TILE_MASKS
+  // The masked single-scene kernels: every kernel argument the prologue and the final store read is asked for
+  // here, so the compiler issues their loads together at entry, behind ONE wait (left to itself it sinks each
+  // load into the block of its first use: four dependent trips before the first camera-table load, and one
+  // for out / stride behind the whole trace).  No instruction; the values are wave-uniform scalars.
+  if constexpr (MODE == RT_MODE_REFL)
+    asm volatile("" ::"s"(recs), "s"(masks), "s"(order), "s"(S.width), "s"(S.height), "s"(n_rows), "s"(y_first),
+                 "s"(band_rows), "s"(band_pitch), "s"(S.cam_sx), "s"(S.cam_sy), "s"(out), "s"(stride), "s"(rgb),
+                 "s"(S.cam.center[0]), "s"(S.cam.center[1]), "s"(S.cam.center[2]), "s"(S.cam.direction[0]),
+                 "s"(S.cam.direction[1]), "s"(S.cam.direction[2]), "s"(S.cam.right[0]), "s"(S.cam.right[1]),
+                 "s"(S.cam.right[2]), "s"(S.cam.up[0]), "s"(S.cam.up[1]), "s"(S.cam.up[2]));
+#endif
+  unsigned tile;
   int x, r;
-  tile_pixel(tile, lane, S.width, &x, &r);
+  TileMask tm = tile_mask_ones();
+  if (recs) {
+    // The entry's dispatch record (rt_blob.h RtTileRec): one 32-byte scalar load at an address made of a kernel
+    // argument and the workgroup id -- the tile's first pixel (no order entry, no division) and its mask
+    // words.  The records hold the launch's order; a calibrating launch has none (entry e is tile e).
+    const cptr<RtTileRec> R = as_const(recs) + entry;
+    tile = entry;
+    x = R->x0 + lane % RT_TILE_W;
+    r = R->r0 + lane / RT_TILE_W;
+    for (int k = 0; k < RT_TILEMASK_WORDS; ++k) tm.w[k] = R->mask[k];
+  } else {
+    tile = CAL || !order ? entry : (unsigned)order[entry];
+    tile_pixel(tile, lane, S.width, &x, &r);
+    if (masks) {                            // the tile's row of the mask table; the tile index is the same in every lane
+      const cptr<uint32_t> tw = as_const(masks) + (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)tile) * RT_TILEMASK_WORDS;
+      for (int k = 0; k < RT_TILEMASK_WORDS; ++k) tm.w[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)tw[k]);
+    }
+  }
   if (x >= S.width || r >= n_rows) return;
   const int y = band_row(r, y_first, band_rows, band_pitch, n_rows);
   if (y >= S.height) return;
   V3 ro, rd;
   camera_ray_px(S, x, y, &ro, &rd);                                         // get_pixel(x as f64, y as f64)
-  // the tile's mask words (null: all ones); the tile index is the same in every lane
-  const uint32_t* tmask =
-      masks ? masks + (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)tile) * RT_TILEMASK_WORDS : nullptr;
   const Col c = trace<REFR, NoRec, KL, FC, KLR, CHAIN, KP>(make_ds(S), ro, rd, max_depth, nullptr, PRIM ? nullptr : frames + lane,
-                                                         frames, tmask);
+                                                         frames, tm);
   store_pixel<F64, PRIM>(out + (size_t)r * stride, x, c, rgb);
   if constexpr (CAL)
     if (threadIdx.x == 0) cost[tile] = (uint32_t)(wall_clock64() - t_start);   // vector store
@@ -1864,9 +1911,10 @@ template <int MODE, bool F64, bool CAL, bool FC, int KL_ = -1, int KP_ = -1, boo
 __device__ __forceinline__ void rows_body(const RtDevScene& S, int y_first, int band_rows, int band_pitch, int n_rows,
                                           int max_depth, uint8_t* __restrict__ out, size_t stride,
                                           const int32_t* __restrict__ order, uint32_t* __restrict__ cost, int rgb,
-                                          lds_f64* frames, const uint32_t* __restrict__ masks = nullptr) {
+                                          lds_f64* frames, const uint32_t* __restrict__ masks = nullptr,
+                                          const RtTileRec* __restrict__ recs = nullptr) {
   rows_entry<MODE, F64, CAL, FC, KL_, KP_, PRIM>(S, blockIdx.x, y_first, band_rows, band_pitch, n_rows, max_depth, out,
-                                                 stride, order, cost, rgb, frames, masks);
+                                                 stride, order, cost, rgb, frames, masks, recs);
 }
 // Two-eye cameras (StereoscopicCamera / AnaglyphCamera, camera.rs:82-205; rt_blob.h RtViews): one launch
 // over the tiles of two views.  Entry e (or the order's e-th) is tile e of view 0 for e < tiles0, else
@@ -1917,8 +1965,7 @@ __device__ __forceinline__ void rows_views_body(const RtDevScene& S, const RtVie
   const double sx = V.cam_sx[xv], sy = S.cam_sy[y];                          // create_ray(xv as f64, y as f64)
   const V3 rd = add(add(ld3(V.cam.direction), scale(ld3(V.cam.right), sx)), scale(ld3(V.cam.up), sy));
   const V3 ro = ld3(V.cam.center);
-  const Col c = trace<REFR, NoRec, KL, FC, KLR, CHAIN, KP>(make_ds(S), ro, rd, max_depth, nullptr, frames + lane, frames,
-                                                         nullptr);
+  const Col c = trace<REFR, NoRec, KL, FC, KLR, CHAIN, KP>(make_ds(S), ro, rd, max_depth, nullptr, frames + lane, frames);
   store_pixel_view<F64>(out + (size_t)r * stride, V.x0 + xv, c, rgb, V.channels);
   if constexpr (CAL)
     if (threadIdx.x == 0) cost[entry] = (uint32_t)(wall_clock64() - t_start);   // vector store
@@ -1949,8 +1996,7 @@ __device__ __forceinline__ void points_body(const RtDevScene& S, const double* _
   if (i >= n) return;
   V3 ro, rd;
   camera_ray(S.cam, xy[2 * i], xy[2 * i + 1], &ro, &rd);
-  const Col c = trace<REFR, NoRec, KL, FC, KLR, CHAIN, KP>(make_ds(S), ro, rd, max_depth, nullptr, frames + lane, frames,
-                                                         nullptr);
+  const Col c = trace<REFR, NoRec, KL, FC, KLR, CHAIN, KP>(make_ds(S), ro, rd, max_depth, nullptr, frames + lane, frames);
   out[4 * i] = c.r; out[4 * i + 1] = c.g; out[4 * i + 2] = c.b; out[4 * i + 3] = 1.0;
 }
 // Request i of an anti-aliasing pass: req[2 * i] = the edge pixel's index e, req[2 * i + 1] = sx | sy << 8;
@@ -1972,8 +2018,7 @@ __device__ __forceinline__ void aa_trace_body(const RtDevScene& S, const uint32_
   const int sx = s & 0xff, sy = s >> 8;
   V3 ro, rd;
   camera_ray(S.cam, (double)x + ((double)sx / (double)size), (double)y + ((double)sy / (double)size), &ro, &rd);
-  const Col c = trace<REFR, NoRec, KL, FC, KLR, CHAIN, KP>(make_ds(S), ro, rd, max_depth, nullptr, frames + lane, frames,
-                                                         nullptr);
+  const Col c = trace<REFR, NoRec, KL, FC, KLR, CHAIN, KP>(make_ds(S), ro, rd, max_depth, nullptr, frames + lane, frames);
   double* o = col + ((size_t)e * size * size + sx * size + sy) * 4;
   o[0] = c.r; o[1] = c.g; o[2] = c.b; o[3] = 1.0;
 }

@@ -302,7 +302,12 @@ static std::string spec_kernel(int kind, int mode, bool fc, int f64, int cal) {
       "(RtDevScene S, int y_first, int band_rows, int band_pitch, int n_rows, int max_depth, uint8_t* __restrict__ out, "
       "size_t stride, const int32_t* __restrict__ order, uint32_t* __restrict__ cost, int rgb";
   // the megakernel and the primary-ray kernel also take the launch geometry's tile-mask table (null: all ones)
-  const std::string args_m = std::string(args) + ", const uint32_t* __restrict__ masks)", args_d = std::string(args) + ")";
+  // -- and, in a masked program of a reflection-only scene (rt_device.h RT_REC_PARAMS: empty elsewhere), its dispatch
+  // records; the mask-free megakernel (kind 3, RT_TILE_MASKS 0) keeps the signature without them
+  const bool recs = mode == RT_MODE_REFL && (kind == 0 || kind == 2 || kind == 3);
+  const std::string args_m = std::string(args) + ", const uint32_t* __restrict__ masks" + (recs ? " RT_REC_PARAMS)" : ")"),
+                    args_d = std::string(args) + ")";
+  const char* rec_args = recs ? " RT_REC_ARGS" : "";
   char buf[1280], waves[64];
   // The specialised megakernel runs 4 waves/SIMD (128 VGPRs): its unrolled walks keep more values
   // live than the generic loop, and at the generic reflection kernel's 5 waves (96 VGPRs) it spilled
@@ -338,16 +343,17 @@ static std::string spec_kernel(int kind, int mode, bool fc, int f64, int cal) {
              "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(%d))) "
              "void rt_spec_prim_%d%d%s {\n"
              "  rows_body<%d, %s, %s, %s, 0, 0, true>(S, y_first, band_rows, band_pitch, n_rows, 0, out, stride, order, "
-             "cost, rgb, nullptr, masks);\n}\n",
-             RT_SPEC_WAVES_PRIM, f64, cal, args_m.c_str(), mode, f64 ? "true" : "false", cal ? "true" : "false", fc ? "true" : "false");
+             "cost, rgb, nullptr, masks%s);\n}\n",
+             RT_SPEC_WAVES_PRIM, f64, cal, args_m.c_str(), mode, f64 ? "true" : "false", cal ? "true" : "false", fc ? "true" : "false",
+             rec_args);
   else if (kind == 0 || kind == 3)    // 3: the megakernel of the mask-free program (spec_programs), a null table
     snprintf(buf, sizeof buf,
              "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(%s))) "
              "void rt_spec_rows_%d%d%s {\n  __shared__ double s_frames[rows_lds_doubles<%d, %d, %d>()];\n"
              "  rows_body<%d, %s, %s, %s, %d, %d>(S, y_first, band_rows, band_pitch, n_rows, max_depth, out, stride, order, "
-             "cost, rgb, (lds_f64*)s_frames, %s);\n}\n",
+             "cost, rgb, (lds_f64*)s_frames, %s%s);\n}\n",
              waves, f64, cal, args_m.c_str(), mode, kl, kp, mode, f64 ? "true" : "false", cal ? "true" : "false", fc ? "true" : "false",
-             kl, kp, kind == 3 ? "nullptr" : "masks");
+             kl, kp, kind == 3 ? "nullptr" : "masks", rec_args);
   else
     snprintf(buf, sizeof buf,
              "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RT_WAVES_PER_EU_DEFERRED))) "

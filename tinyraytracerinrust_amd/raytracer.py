@@ -454,6 +454,11 @@ class Renderer:
         v = (2 if mode else 0) if isinstance(mode, bool) else int(mode)
         check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_TILE_MASKS, v))
 
+    def set_tile_records(self, on: bool) -> None:
+        """rt_ctx_set_option(RT_OPT_TILE_RECORDS): masked launches read one dispatch record per order entry
+        (the default), or the tile order and the tile-indexed mask table themselves (same pixels)."""
+        check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_TILE_RECORDS, 1 if on else 0))
+
     def tile_masks(self, y_first: int = 0, band_rows: Optional[int] = None, band_pitch: Optional[int] = None,
                    n_bands: int = 1) -> np.ndarray:
         """rt_ctx_tile_masks: the uploaded scene's mask table of a band launch (default: the whole frame)

@@ -3,7 +3,8 @@
 the specialised kernels loaded (RT_OPT_SPECIALIZE 1, rt_ctx_spec_wait) unless --generic.  Prints the
 ms per frame (one event pair around --frames launches) per library, median over --rounds.
 usage: python tools/ab_libs.py LIB [LIB ...] [--config sphere1080d0|globes1080d5|globes4k|spin1080|fractal1080] [--generic]
-       [--masks=-1,1,0]   per library: RT_OPT_TILE_MASKS (-1: leave it, for libraries without the option)"""
+       [--masks=-1,1,0]   per library: RT_OPT_TILE_MASKS (-1: leave it, for libraries without the option)
+       [--records=-1,1,0] per library: RT_OPT_TILE_RECORDS (-1: leave it)"""
 import argparse
 import ctypes
 import os
@@ -30,6 +31,7 @@ def main():
     ap.add_argument("--levels", default="", help="per library (in order): its RT_OPT_SPECIALIZE level, e.g. 1,2 "
                                                    "(a library path may repeat); default 1 (0 with --generic)")
     ap.add_argument("--masks", default="", help="per library (in order): RT_OPT_TILE_MASKS, -1 = leave the default")
+    ap.add_argument("--records", default="", help="per library (in order): RT_OPT_TILE_RECORDS, -1 = leave the default")
     a = ap.parse_args()
     import torch
     scene, W, H, depth = CONFIGS[a.config]
@@ -37,7 +39,8 @@ def main():
     ctxs, outs = [], []
     levels = [int(v) for v in a.levels.split(",")] if a.levels else [0 if a.generic else 1] * len(a.libs)
     masks = [int(v) for v in a.masks.split(",")] if a.masks else [-1] * len(a.libs)
-    for path, level, mask in zip(a.libs, levels, masks):
+    records = [int(v) for v in a.records.split(",")] if a.records else [-1] * len(a.libs)
+    for path, level, mask, rec in zip(a.libs, levels, masks, records):
         L = ctypes.CDLL(os.path.abspath(path), mode=os.RTLD_LOCAL)
         L.rt_ctx_spec_wait.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         sc, cx = ctypes.c_void_p(), ctypes.c_void_p()
@@ -46,6 +49,8 @@ def main():
         assert L.rt_ctx_set_option(cx, 6, level) == 0
         if mask >= 0:
             assert L.rt_ctx_set_option(cx, 8, mask) == 0               # RT_OPT_TILE_MASKS
+        if rec >= 0:
+            assert L.rt_ctx_set_option(cx, 10, rec) == 0              # RT_OPT_TILE_RECORDS
         assert L.rt_ctx_upload(cx, sc) == 0
         assert L.rt_ctx_spec_wait(cx, -1) == 0
         assert L.rt_ctx_set_option(cx, 1, 0) == 0                  # RT_OPT_TIMING off, as bench.py
@@ -86,10 +91,10 @@ def main():
         if not a.no_check and not torch.equal(outs[i], outs[0]):
             raise SystemExit(f"{a.libs[i]}: frame differs from {a.libs[0]}'s")
     print(f"{a.config} ({'generic' if a.generic else 'specialised'}), {n} frames per measurement, ms per frame, median of {a.rounds}:")
-    for path, level, mask, v in zip(a.libs, levels, masks, res):
+    for path, level, mask, rec, v in zip(a.libs, levels, masks, records, res):
         w = sorted(v)
         print(f"  {w[len(w) // 2]:.4f}  ({' '.join(f'{x:.4f}' for x in v)})  {path} (RT_OPT_SPECIALIZE {level}"
-              f"{'' if mask < 0 else f', RT_OPT_TILE_MASKS {mask}'})", flush=True)
+              f"{'' if mask < 0 else f', RT_OPT_TILE_MASKS {mask}'}{'' if rec < 0 else f', RT_OPT_TILE_RECORDS {rec}'})", flush=True)
 
 
 if __name__ == "__main__":

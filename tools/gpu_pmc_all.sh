@@ -18,7 +18,7 @@ for C in $CONFIGS; do
     anim120) ARGS="--config anim120 --steps 1 --warmup 0 --no-cpu-baseline"; LIM=240 ;;
     *) ARGS="--config $C --steps 5 --warmup 1 --no-cpu-baseline --no-extra"; LIM=150 ;;
   esac
-  for PMC in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64" "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES" "SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE GRBM_COUNT"; do
+  for PMC in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64" "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_INSTS_SALU SQ_INSTS_SMEM" "SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE GRBM_COUNT"; do
     N=$(echo $PMC | tr ' ' '_' | cut -c1-40)
     timeout -s KILL $LIM rocprofv3 --pmc $PMC --output-format csv -d $O/${T}_${C}_pmc_$N -o run -- python3 bench.py $ARGS > /dev/null 2> $O/${T}_${C}_pmc_$N.err || { echo "pmc $C $PMC failed"; tail $O/${T}_${C}_pmc_$N.err; exit 1; }
   done

@@ -73,7 +73,7 @@ def main(tag="r01", config="globes4k", kernel="render_rows_kernel"):
         # the per-launch counters bench.py's roofline.issue block is derived from
         keep = ("SQ_INSTS_VALU", "SQ_INSTS_VALU_ADD_F64", "SQ_INSTS_VALU_MUL_F64", "SQ_INSTS_VALU_FMA_F64",
                 "SQ_INSTS_VALU_TRANS_F64", "SQ_WAVES", "SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY",
-                "SQ_ACTIVE_INST_ANY", "SQ_ACTIVE_INST_VALU", "GRBM_GUI_ACTIVE", "GRBM_COUNT")
+                "SQ_ACTIVE_INST_ANY", "SQ_ACTIVE_INST_VALU", "GRBM_GUI_ACTIVE", "GRBM_COUNT", "SQ_INSTS_SALU", "SQ_INSTS_SMEM")
         summ[f"{config}/n1/contiguous"]["counters"] = {k: mean[k] for k in keep if k in mean}
         with open(summ_path, "w") as f:
             json.dump(summ, f, indent=1)
