@@ -46,7 +46,7 @@ def test_static_scene_rebuilt_every_frame(worldmap):
         f, info, dt = _frame(r, text, 0.0)
         assert_close(f, None, ref, None, f"rebuild {k} ({info})")
         # rebuild 0 may calibrate once more: an order the generic kernels built for a launch this small
-        # chose the deferred kernel, which the loaded program drops (spec.hip spec_poll)
+        # chose the deferred kernel, which the loaded program drops (spec_ctx.hip spec_poll)
         if k:
             assert "(specialised)" in info and "process cache" in info, info
             ms.append(dt)

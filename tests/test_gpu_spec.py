@@ -1,4 +1,4 @@
-"""Scene-specialised row kernels (tinyraytracerinrust_amd/csrc/spec.hip, RT_OPT_SPECIALIZE): the same
+"""Scene-specialised row kernels (tinyraytracerinrust_amd/csrc/spec_text.cpp, spec_ctx.hip; RT_OPT_SPECIALIZE): the same
 device code as the generic kernels, compiled by hipRTC with the uploaded scene's tables as constants.
 Every frame against the CPU oracle (a restatement of src/raytracer/raytracer.rs:132-287), RGBA8
 bit-identical -- and at level 2 (f64 and calibration launches specialised too) the f64 colours

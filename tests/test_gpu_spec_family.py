@@ -1,4 +1,4 @@
-"""Scene families (rt_spec_family_register, csrc/spec.hip; rt_device.h RT_REC): one specialised program
+"""Scene families (rt_spec_family_register, csrc/spec_text.cpp; rt_device.h RT_REC): one specialised program
 per family of scenes of the same structure -- the frames of an animation (the reference's animate
 mode, gui.rs:78-89, builds every frame's scene anew) -- the words every member shares compiled in,
 the others read from the rendering scene's own tables.  Every frame against the CPU oracle (a

@@ -1,4 +1,4 @@
-"""The sample programs on the GPU (tinyraytracerinrust_amd/csrc/spec.hip rt_spec_points / rt_spec_aa,
+"""The sample programs on the GPU (tinyraytracerinrust_amd/csrc/spec_text.cpp rt_spec_points / rt_spec_aa,
 RT_OPT_SPEC_SAMPLES): rt_render_points_f64 and the anti-aliasing trace through the scene-specialised device
 code -- the unrolled walks over literal f32 boxes and the inlined texel guard the full frames render with.
 

@@ -1,4 +1,4 @@
-"""The scene-specialised program (tinyraytracerinrust_amd/csrc/spec.hip, RT_OPT_SPECIALIZE) on the CPU:
+"""The scene-specialised program (tinyraytracerinrust_amd/csrc/spec_text.cpp, RT_OPT_SPECIALIZE) on the CPU:
 its text carries the flattened scene's records bit for bit, and hipRTC compiles it without a device
 (rt_scene_precompile).  The pixels it renders are checked on the GPU (tests/test_gpu_spec.py)."""
 import os
@@ -110,7 +110,7 @@ def test_compiler_origin_and_resources_after_torch():
 
 
 def test_guard_bounds_hold_for_the_benchmark_programs():
-    """The resource guard (spec.hip RT_SPEC_MAX_*) accepts the programs the benchmark configs run --
+    """The resource guard (spec_compile.cpp RT_SPEC_MAX_*) accepts the programs the benchmark configs run --
     globes.scene's megakernel and deferred kernel -- and reports what hipRTC built."""
     comp, ks = _report(scene_text("globes"))
     assert "ROCm installation" in comp, comp

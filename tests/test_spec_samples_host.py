@@ -1,4 +1,4 @@
-"""The sample programs (tinyraytracerinrust_amd/csrc/spec.hip rt_spec_points / rt_spec_aa, RT_OPT_SPEC_SAMPLES)
+"""The sample programs (tinyraytracerinrust_amd/csrc/spec_text.cpp rt_spec_points / rt_spec_aa, RT_OPT_SPEC_SAMPLES)
 on the CPU: the ABI's new symbols, and the two kernels hipRTC builds for a scene without a device
 (rt_scene_sample_report), inside the resource guard's bounds of the scene's mode -- while the row programs
 stay the three that rt_scene_spec_report names.  What they render is checked on the GPU
@@ -8,7 +8,7 @@ import inspect
 
 from tests.conftest import SCENES, scene_text
 
-MAX_VGPRS, MAX_SCRATCH_ROWS = 128, 1024       # spec.hip RT_SPEC_MAX_VGPRS, RT_SPEC_MAX_SCRATCH_ROWS (reflection, chain)
+MAX_VGPRS, MAX_SCRATCH_ROWS = 128, 1024       # spec_compile.cpp RT_SPEC_MAX_VGPRS, RT_SPEC_MAX_SCRATCH_ROWS (reflection, chain)
 
 
 def _lines(report):

@@ -171,7 +171,7 @@ void drop_records(rt_ctx* c) {
 }
 
 // The mask plane: the first object in draw order that is one plane leaf whose constant unit normal the
-// host formed (RtObject::unit_normal); the specialised program holds the same index (spec.hip MASK_PLANE).
+// host formed (RtObject::unit_normal); the specialised program holds the same index (spec_text.cpp MASK_PLANE).
 int tilemask_plane(const FlatScene& f) {
   if (f.objects.size() > RT_TILEMASK_OBJECTS) return -1;
   for (size_t o = 0; o < f.objects.size(); ++o) {

@@ -3,7 +3,7 @@
 // that its traversals cull with the specialised programs' f32 slab tests (RT_CULL_F32, rt_device.h
 // fbox_may_hit) on the same outward-rounded boxes: the edge tests (tests/test_gpu_cull_edges.py,
 // test_gpu_texel_boundary.py) aim rays at silhouettes and shadow edges -- the culling decisions closest
-// to a box -- through this kernel.  A context whose scene has a specialised points kernel loaded (spec.hip
+// to a box -- through this kernel.  A context whose scene has a specialised points kernel loaded (spec_text.cpp
 // rt_spec_points, RT_OPT_SPEC_SAMPLES) launches that instead: the specialised programs' own walks, which
 // tests/test_gpu_spec_samples.py aims the same rays at.
 #ifndef RT_CULL_F32
@@ -99,12 +99,12 @@ int rt_render_points_f64(rt_ctx* c, const double* xy, size_t n, int32_t max_dept
     if (!dev_out) target = sx + 2 * n;
   }
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  // the scene's specialised points kernel (spec.hip rt_spec_points: one-wave workgroups), once it is loaded;
+  // the scene's specialised points kernel (spec_text.cpp rt_spec_points: one-wave workgroups), once it is loaded;
   // a launch of 2^31 samples or more keeps the generic kernel (the module launch's work size is 32 bits)
-  hipFunction_t sfn = spec_sample_kernel(c, RT_SAMPLE_POINTS);
+  hipFunction_t sfn = spec_sample_kernel(c, SPEC_POINTS);
   if (sfn && n >= ((size_t)1 << 31)) {
     sfn = nullptr;
-    c->last_sample = "points";
+    c->spec.last_sample = "points";
   }
   if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
   if (sfn) {

@@ -205,14 +205,15 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   const uint32_t* mask_table = nullptr;
   const void* mask_slot = nullptr;
   const RtTileRec* rec_table = nullptr;       // the launch's dispatch records (RT_OPT_TILE_RECORDS), gathered from both
-  if (c->spec_mod && !refr && c->spec_mode == RT_MODE_REFL && !c->spec_family && c->dev.n_objects <= 32 &&
-      (c->dev.colour_fast != 0 && c->fast_clamp) == c->spec_fc) {
+  const rt::SpecProgram& sp = c->spec.prog;
+  if (c->spec.loaded && !refr && sp.mode == RT_MODE_REFL && !sp.family && c->dev.n_objects <= 32 &&
+      (c->dev.colour_fast != 0 && c->fast_clamp) == sp.fc) {
     // RT_OPT_TILE_MASKS 1: the primary-ray kernel always takes the table (its one walk per pixel only gains);
     // the megakernel where the geometry's calibration found the launch throughput-bound (OrderSlot::masks_pay).
     // A launch without a measured order (too small, calibrating, tile order off) takes none.  2: every launch.
-    const bool prim0 = max_depth == 0 && dmode != 1 && c->spec_prim[f64 ? 1 : 0][calibrate ? 1 : 0];
+    const bool prim0 = max_depth == 0 && dmode != 1 && spec_fn(c, SPEC_PRIMARY, f64, calibrate);
     const bool want = c->tile_masks == 2 || (c->tile_masks == 1 && (prim0 || (order && slot->masks_pay)));
-    if (want && (prim0 || (!deferred && c->spec_rows[f64 ? 1 : 0][calibrate ? 1 : 0])))
+    if (want && (prim0 || (!deferred && spec_fn(c, SPEC_ROWS, f64, calibrate))))
       RT_TRY(launch_masks(c, st, a0, a1, a2, a3, n_tiles, &mask_table, &mask_slot));
     // (a deferred slot's entries carry split parts: no plain tiles to gather)
     if (mask_table && c->tile_records && !(order && slot->deferred))
@@ -266,16 +267,15 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   const bool tune = order && tree && dmode == -1 && slot->wf_tune == 0;
   if (tune) RT_HIP(hipEventRecord(c->tev0, st));
   const int mode = chain ? RT_MODE_CHAIN : refr ? RT_MODE_TREE : RT_MODE_REFL;
-  // the scene-specialised kernel of this launch (spec.hip), when the context holds one that matches
+  // the scene-specialised kernel of this launch (spec_ctx.hip), when the context holds one that matches
   hipFunction_t sfn = nullptr;
   bool prim = false;
-  if (c->spec_mod && mode == c->spec_mode && fc == c->spec_fc) {
+  if (c->spec.loaded && mode == sp.mode && fc == sp.fc) {
     // launches of primary rays only (max_depth 0) take the program's primary-ray kernel (no frame stack,
     // rt_device.h PRIM) unless the deferred kernel was asked for
-    prim = max_depth == 0 && dmode != 1 && c->spec_prim[f64 ? 1 : 0][calibrate ? 1 : 0];
+    prim = max_depth == 0 && dmode != 1 && spec_fn(c, SPEC_PRIMARY, f64, calibrate);
     if (prim) deferred = false;
-    sfn = prim ? c->spec_prim[f64 ? 1 : 0][calibrate ? 1 : 0]
-               : deferred ? c->spec_def[f64 ? 1 : 0][calibrate ? 1 : 0] : c->spec_rows[f64 ? 1 : 0][calibrate ? 1 : 0];
+    sfn = spec_fn(c, prim ? SPEC_PRIMARY : deferred ? SPEC_DEFERRED : SPEC_ROWS, f64, calibrate);
   }
   c->last_kernel = prim ? "primary-ray (specialised)"
                         : deferred ? (sfn ? "deferred (specialised)" : "deferred") : (sfn ? "megakernel (specialised)" : "megakernel");
@@ -292,13 +292,13 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   c->last_masked = masks != nullptr;
   const RtTileRec* recs = masks ? rec_table : nullptr;
   c->last_records = recs != nullptr;
-  // a megakernel launch without a table runs the program's mask-free megakernel (spec.hip kind 3)
-  if (sfn && !prim && !deferred && !masks && c->spec_rows_nm[f64 ? 1 : 0][calibrate ? 1 : 0])
-    sfn = c->spec_rows_nm[f64 ? 1 : 0][calibrate ? 1 : 0];
+  // a megakernel launch without a table runs the program's mask-free megakernel (SPEC_ROWS_NOMASK)
+  if (sfn && !prim && !deferred && !masks && spec_fn(c, SPEC_ROWS_NOMASK, f64, calibrate))
+    sfn = spec_fn(c, SPEC_ROWS_NOMASK, f64, calibrate);
   if (sfn) {
     void* kargs[] = {&c->dev, (void*)&a0, (void*)&a1, (void*)&a2, (void*)&a3, &max_depth, &target, &tstride,
                      (void*)&order, &cost, (void*)&rgbi, (void*)&masks, (void*)&recs};   // (a kernel reads as
-    // many as it declares: the masked single-scene kernels take the records, spec.hip)
+    // many as it declares: the masked single-scene kernels take the records, spec_text.cpp)
     // hipExtModuleLaunchKernel takes the global work size in work-items (grid x 64)
     RT_HIP(hipExtModuleLaunchKernel(sfn, grid.x * 64u, 1, 1, 64, 1, 1, 0, st, kargs, nullptr, nullptr, mev, 0));
   }
@@ -368,7 +368,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
     // (tail ratios 1.6 / 3.0) 0.109 / 0.098 ms against 0.156 / 0.117 ms deferred, 1080p d5 (ratio 1.6)
     // 0.104 against 0.136 ms (profiles/r06d_kernel_choice.txt): the tail-bound choice is for the
     // generic kernels only.
-    const bool spec_mega = c->spec_mod && c->spec_mode == RT_MODE_REFL && c->spec_rows[f64 ? 1 : 0][0] && fc == c->spec_fc;
+    const bool spec_mega = sp.mode == RT_MODE_REFL && spec_fn(c, SPEC_ROWS, f64, false) && fc == sp.fc;
     if (auto_ok && dmode == -1 && n_tiles < RT_DEFERRED_MAX_TILES && !spec_mega) {
       uint64_t sum = 0, mx = 0;
       for (uint32_t v : h_cost) { sum += v; mx = v > mx ? v : mx; }

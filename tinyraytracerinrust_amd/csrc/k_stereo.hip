@@ -85,8 +85,7 @@ int launch_views(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, int 
   if (pooled && RT_POOL_OBJ_INDEX && c->dev.n_objects > 256)
     return fail(RT_ERR_UNSUPPORTED, "a pooled kernel for a scene of %d objects (one-byte object index)", c->dev.n_objects);
   hipFunction_t sfn = nullptr;
-  if (c->spec_mod && c->spec_two_eyes && mode == c->spec_mode && fc == c->spec_fc)
-    sfn = c->spec_views[f64 ? 1 : 0][calibrate ? 1 : 0];
+  if (c->spec.prog.two_eyes && mode == c->spec.prog.mode && fc == c->spec.prog.fc) sfn = spec_fn(c, SPEC_VIEWS, f64, calibrate);
   c->last_kernel = sfn ? "view megakernel (specialised)" : "view megakernel";
   if (sfn) {
     void* kargs[] = {&c->dev, &vw, (void*)&a0, (void*)&a1, (void*)&a2, (void*)&a3, &max_depth, &target, &tstride,

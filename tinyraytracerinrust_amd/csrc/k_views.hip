@@ -413,10 +413,10 @@ int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double 
   hipStream_t st = (hipStream_t)stream;
   // the trace passes' kernel: the scene's specialised one once it is loaded (requested here on the first call
   // after an upload, polled without blocking); last_sample names it only if a pass launches
-  const char* const sample_before = c->last_sample;
-  const hipFunction_t sfn = spec_sample_kernel(c, RT_SAMPLE_AA);
-  const char* const sample_ran = c->last_sample;
-  c->last_sample = sample_before;
+  const char* const sample_before = c->spec.last_sample;
+  const hipFunction_t sfn = spec_sample_kernel(c, SPEC_AA);
+  const char* const sample_ran = c->spec.last_sample;
+  c->spec.last_sample = sample_before;
   const size_t npx = (size_t)W * H;
   // device staging: [src u8][dst u8][dst f64][edges][counters] for host pointers
   const bool d_src = is_device_ptr(src_rgba8), d_u8 = !dst_rgba8 || is_device_ptr(dst_rgba8);
@@ -479,9 +479,9 @@ int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double 
       rays += n_req;
       const dim3 rg((n_req + 63) / 64);
       const bool fc = c->dev.colour_fast != 0 && c->fast_clamp;
-      c->last_sample = sample_ran;
+      c->spec.last_sample = sample_ran;
 #define RT_LAUNCH_AA(R, F) hipLaunchKernelGGL((aa_trace_kernel<R, F>), rg, dim3(64), 0, st, c->dev, G, edges, req, n_req, (int)max_depth)
-      if (sfn) {                                                 // the scene's specialised trace kernel (spec.hip rt_spec_aa)
+      if (sfn) {                                                 // the scene's specialised trace kernel (the catalogue's rt_spec_aa)
         int depth = max_depth, size = sz;
         double* col = (double*)G.col;
         void* kargs[] = {&c->dev, (void*)&edges, (void*)&req, &n_req, &size, &col, &depth};

@@ -13,8 +13,8 @@
 
 #include "rt_blob.h"
 #include "scene.h"
+#include "spec.h"
 
-namespace rt { struct SpecJob; }        // spec.hip: one program's compile, shared by the contexts that want it
 
 struct rt_ctx {
   int device = 0;
@@ -120,50 +120,41 @@ struct rt_ctx {
   bool masks_ok = false;                // the uploaded scene has a mask scene in its blob (<= 32 objects)
   const void* d_mask_scene = nullptr;   // RtTileMaskScene in the blob
   bool last_masked = false;             // the last row launch passed a mask table (rt_ctx_kernel_info)
-  // Scene-specialised row kernels (spec.hip, rt_ctx_set_option(RT_OPT_SPECIALIZE)): hipRTC compiles
-  // rt_device.h with this scene's tables as constexpr data, in the background (the library's compile
-  // pool); launches take them once they are loaded (spec_poll), the generic kernels until then.
-  int spec_on = 1;                      // RT_OPT_SPECIALIZE: 0 off, 1 (default) product launches, 2 every row launch
-  std::string spec_src;                 // the program's prelude (spec_source, or a registered family's)
-  int spec_mode = 0;                    // RT_MODE_* of the uploaded scene
-  bool spec_fc = false;                 // the program's clamp form (RtDevScene::colour_fast)
-  bool spec_deferred = false;           // the program also holds the deferred kernels
-  bool spec_fits = false;               // small enough to specialise (RT_SPEC_MAX_OBJECTS / _LEAVES)
-  hipModule_t spec_mod = nullptr;       // non-null once the kernels are loaded (null: generic kernels)
-  hipModule_t spec_mods[16] = {};       // one module per specialised kernel, on this context's device
-  hipFunction_t spec_rows[2][2] = {};   // [f64][cal]
-  hipFunction_t spec_rows_nm[2][2] = {};   // [f64][cal]: the megakernel compiled WITHOUT the tile-mask operand (a null
-                                        // table folded at compile time: the walks of a program without masks), for
-                                        // launches that take no table; reflection-only single-scene programs only
-  hipFunction_t spec_def[2][2] = {};    // [f64][cal]
-  hipFunction_t spec_views[2][2] = {};  // [f64][cal]: the view megakernel (two-eye scenes; their programs hold nothing else)
-  bool spec_two_eyes = false;           // the program is a two-eye scene's (spec_flags): view kernels only
-  hipFunction_t spec_prim[2][2] = {};   // [f64][cal]: the primary-ray kernel (max_depth 0 launches)
-  uint64_t spec_hash = 0;               // FNV-1a of the prelude (kernel info only; caches compare full texts)
-  double spec_compile_ms = 0.0;         // the hipRTC time of the loaded programs (0: read from the disk cache)
-  int spec_family = 0;                  // > 0: the program of a registered scene family of that many members
-  std::shared_ptr<rt::FlatScene> spec_flat;   // the uploaded scene's tables (texels dropped): the program is
+  // Scene-specialised kernels (spec.h, rt_ctx_set_option(RT_OPT_SPECIALIZE)): hipRTC compiles rt_device.h
+  // with this scene's tables as constexpr data, in the background (the library's compile pool); launches
+  // take them once they are loaded (spec_poll), the generic kernels until then.
+  // One slot per kernel of the catalogue, (kind, f64, cal).  The row kinds are one job set, loaded all or
+  // nothing (`loaded`; a failure drops them and sets `error`).  The sample kinds (rt_render_points_f64 and
+  // rt_antialias' trace passes, RT_OPT_SPEC_SAMPLES) are a second: requested by the first such call after an
+  // upload (and by every later upload once a context has asked), behind the row programs in the pool; each
+  // loads, fails and is reported on its own, and nothing of theirs touches the row programs' state.
+  struct SpecSlot {
+    std::shared_ptr<rt::SpecJob> job;   // requested, not yet loaded
+    hipModule_t module = nullptr;       // on this context's device
+    hipFunction_t function = nullptr;   // non-null once loaded (null: the generic kernel)
+    std::string error;                  // a sample path: why it stays generic although requested
+    std::string res;                    // the loaded kernel's resources (a sample kernel's: compile time and provenance too)
+    bool cached = false;                // the code object existed in the process when it was requested
+  };
+  struct Spec {
+    int level = 1;                      // RT_OPT_SPECIALIZE: 0 off, 1 (default) product launches, 2 every row launch
+    int samples = 1;                    // RT_OPT_SPEC_SAMPLES
+    rt::SpecProgram prog;               // the uploaded scene's program (spec_describe)
+    std::shared_ptr<rt::FlatScene> flat;   // the uploaded scene's tables (texels dropped): the program is
                                         // chosen when the option is set (families registered since the upload)
-  std::vector<std::shared_ptr<rt::SpecJob>> spec_jobs;   // programs requested, not yet loaded (one per kernel)
-  std::string spec_error;               // why the context keeps the generic kernels although spec_on (kernel info)
-  std::string spec_note;                // " [process cache]" / " [disk cache]"
-  std::string spec_res;                 // the loaded megakernel's resources (kernel info)
-  double spec_t0 = 0.0;                 // when the programs were requested (steady clock, ms)
-  double spec_ready_ms = 0.0;           // request -> loaded, ms
-  // The sample programs (spec.hip rt_spec_points / rt_spec_aa, RT_OPT_SPEC_SAMPLES): the specialised kernels of
-  // rt_render_points_f64 ([0]) and of rt_antialias' trace passes ([1]), a job set of their own beside spec_jobs.
-  // Requested by the first such call after an upload (and by every later upload once a context has asked),
-  // behind the row programs in the pool; each path loads, fails and is reported on its own, and nothing here
-  // touches the row programs' state above.
-  int samp_on = 1;                      // RT_OPT_SPEC_SAMPLES
-  bool samp_wanted = false;             // a points / AA call (or rt_ctx_spec_wait_samples) has asked: uploads request them
-  std::shared_ptr<rt::SpecJob> samp_jobs[2];   // requested, not yet loaded
-  hipModule_t samp_mods[2] = {};
-  hipFunction_t samp_fn[2] = {};        // non-null once loaded (null: the generic kernel)
-  std::string samp_error[2];            // why a path stays generic although requested
-  std::string samp_res[2];              // a loaded kernel's resources, compile time and provenance (sample kernel info)
-  bool samp_cached[2] = {};             // the code object existed in the process when it was requested
-  const char* last_sample = "none";     // what the last points / AA trace launch ran (rt_ctx_sample_kernel_info)
+    SpecSlot slots[rt::SPEC_KINDS][2][2];   // [kind][f64][cal]
+    bool pending = false;               // row programs requested, not yet loaded
+    bool loaded = false;                // the row kernels are loaded (false: generic kernels)
+    std::string error;                  // why the context keeps the generic kernels although `level` (kernel info)
+    std::string note;                   // " [process cache]" / " [disk cache]"
+    std::string res;                    // the loaded megakernel's resources (kernel info)
+    uint64_t hash = 0;                  // FNV-1a of the prelude (kernel info only; caches compare full texts)
+    double compile_ms = 0.0;            // the hipRTC time of the loaded programs (0: read from the disk cache)
+    double t0 = 0.0;                    // when the programs were requested (steady clock, ms)
+    double ready_ms = 0.0;              // request -> loaded, ms
+    bool samples_wanted = false;        // a points / AA call (or rt_ctx_spec_wait_samples) has asked: uploads request them
+    const char* last_sample = "none";   // what the last points / AA trace launch ran (rt_ctx_sample_kernel_info)
+  } spec;
   // Completion marks: per stream this context launched on, an event recorded after its last launch
   // there.  rt_ctx_synchronize / option changes / rt_ctx_free wait on them -- never on a caller's
   // stream, which may be destroyed by then.
@@ -180,20 +171,6 @@ using rt::fail;
     if (e_ != hipSuccess) return fail(RT_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); \
   } while (0)
 
-#define RT_TRY(call)                                                                   \
-  do {                                                                                 \
-    const int rc_ = (call);                                                            \
-    if (rc_) return rc_;                                                               \
-  } while (0)
-
-#ifndef RT_SPEC_MAX_OBJECTS
-#define RT_SPEC_MAX_OBJECTS 32
-#endif
-#ifndef RT_SPEC_MAX_LEAVES
-#define RT_SPEC_MAX_LEAVES 48
-#endif
-#define RT_SPEC_MAX_FAMILIES 16
-
 namespace rt {
 // rt_ctx.hip
 void drop_order(rt_ctx::OrderSlot& s);         // frees an order table (hipFree waits for its readers)
@@ -201,7 +178,6 @@ void drop_orders(rt_ctx* c);
 void reset_order_choices(rt_ctx* c);           // a same-structure upload keeps the orders; the ray-tree wavefront choice is timed again
 // k_masks.hip: the tile-mask tables
 void drop_masks(rt_ctx* c);                    // every table (upload, free): hipFree waits for their readers
-int tilemask_plane(const FlatScene& f);        // the mask plane's object index, -1: none
 // The table of the geometry (a0..a3 as launch_wavefront) for a launch on st, filled on st first if it is new
 // since the upload; *table = nullptr when the context takes no masks.
 // (*mslot: the table's slot, for launch_records)
@@ -231,22 +207,20 @@ int launch_views(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, int 
 int mark_event(rt_ctx* c, hipStream_t st, hipEvent_t* ev);   // the event a launch on st binds as its stop event
 int mark_launch(rt_ctx* c, hipStream_t st);                  // record it after work enqueued on st (other launches)
 int wait_launches(rt_ctx* c);
-// spec.hip: the specialised programs of the uploaded scene -- flags (at upload, cheap), the request to the
-// compile pool (asynchronous), the load once compiled (at the next launch, or spec_wait), release
-void spec_flags(const FlatScene& f, rt_ctx* c);     // the scene's mode, clamp form, size limits
-bool same_structure_flat(const FlatScene& a, const FlatScene& b);   // spec.hip: a scene family's structure test
-void spec_prepare(rt_ctx* c, bool retry = false);   // request c's programs (spec_on, spec_flat); returns at once
-int spec_poll(rt_ctx* c);                           // load them if compiled: RT_OK, or RT_PENDING (spec_error on failure)
+// spec_ctx.hip: the specialised programs of the uploaded scene -- the request to the compile pool
+// (asynchronous), the load once compiled (at the next launch, or spec_wait), release
+void spec_prepare(rt_ctx* c, bool retry = false);   // describe and request c's programs (spec.level, spec.flat); returns at once
+int spec_poll(rt_ctx* c);                           // load them if compiled: RT_OK, or RT_PENDING (spec.error on failure)
 int spec_wait(rt_ctx* c, double timeout_ms);        // block (< 0: no limit) then spec_poll
 void spec_drop(rt_ctx* c);                          // unload + release (no launch of c may be in flight)
-const char* spec_compiler();                        // which hipRTC compiles the programs
-// the sample programs (path 0: points, 1: the anti-aliasing trace)
-enum { RT_SAMPLE_POINTS = 0, RT_SAMPLE_AA = 1 };
-void spec_samples_request(rt_ctx* c, bool retry = false);   // ask the pool for them (no-op where they do not apply)
-void spec_samples_poll(rt_ctx* c);                  // load what has compiled (non-blocking)
+// The loaded row kernel of `kind` for (f64, cal), or null (the generic kernels run).
+inline hipFunction_t spec_fn(const rt_ctx* c, int kind, bool f64, bool cal) {
+  return c->spec.loaded ? c->spec.slots[kind][f64 ? 1 : 0][cal ? 1 : 0].function : nullptr;
+}
+// the sample programs (kind: SPEC_POINTS, SPEC_AA)
 int spec_samples_wait(rt_ctx* c, double timeout_ms);   // request, block (< 0: no limit), load: RT_OK / RT_PENDING
 // The kernel of a points / AA call about to launch (the context's device current): requests the programs on the
-// first call, polls, and returns the loaded kernel or null (the generic one runs); sets last_sample.
-hipFunction_t spec_sample_kernel(rt_ctx* c, int path);
+// first call, polls, and returns the loaded kernel or null (the generic one runs); sets spec.last_sample.
+hipFunction_t spec_sample_kernel(rt_ctx* c, int kind);
 std::string spec_sample_info(rt_ctx* c);            // rt_ctx_sample_kernel_info's text
 }  // namespace rt

@@ -262,16 +262,15 @@ int rt_ctx_upload(rt_ctx* c, const rt_scene* s) {
   // masks, which depend on the camera and on every position, were dropped above whatever the structure.
   // The camera kind counts as structure here: a two-eye launch has other tiles (two views') and other
   // kernels, and an upload of a perspective scene after a two-eye one behaves as on a fresh context.
-  if (!(c->spec_flat && prev_kind == f.cam_kind && rt::same_structure_flat(*c->spec_flat, f))) drop_orders(c);
+  if (!(c->spec.flat && prev_kind == f.cam_kind && rt::same_structure_flat(*c->spec.flat, f))) drop_orders(c);
   else rt::reset_order_choices(c);
-  // the scene-specialised programs (spec.hip): requested from the compile pool, loaded by the first
+  // the scene-specialised programs (spec_ctx.hip): requested from the compile pool, loaded by the first
   // launch after they are ready; the generic kernels render until then.  Only the flags are computed
   // here -- the program text (and a family lookup) only when the option is on and the scene fits.
   rt::spec_drop(c);                   // the previous scene's modules (the hipFree above waited for the device)
-  c->spec_flat = std::make_shared<rt::FlatScene>(std::move(f));
-  c->spec_flat->texels.clear();
-  c->spec_flat->texels.shrink_to_fit();
-  rt::spec_flags(*c->spec_flat, c);
+  c->spec.flat = std::make_shared<rt::FlatScene>(std::move(f));
+  c->spec.flat->texels.clear();
+  c->spec.flat->texels.shrink_to_fit();
   rt::spec_prepare(c);
   return RT_OK;
 }
@@ -280,21 +279,22 @@ int rt_ctx_kernel_info(rt_ctx* c, char* buf, size_t cap) {
   if (!c || !buf || cap == 0) return fail(RT_ERR_INVALID, "null argument");
   std::string s;
   char b[1024];
-  if (c->spec_mod) {
+  const rt_ctx::Spec& S = c->spec;
+  if (S.loaded) {
     snprintf(b, sizeof b, "scene-specialised (hipRTC %016llx, %s%s, compiled in %.0f ms%s by %s; %s; loaded %.0f ms after "
-             "the request)", (unsigned long long)c->spec_hash,
-             c->spec_mode == RT_MODE_REFL ? "reflection" : c->spec_mode == RT_MODE_CHAIN ? "chain" : "tree",
-             c->spec_family ? (", family of " + std::to_string(c->spec_family) + " scenes").c_str() : "",
-             c->spec_compile_ms, c->spec_note.c_str(), rt::spec_compiler(), c->spec_res.c_str(), c->spec_ready_ms);
+             "the request)", (unsigned long long)S.hash,
+             S.prog.mode == RT_MODE_REFL ? "reflection" : S.prog.mode == RT_MODE_CHAIN ? "chain" : "tree",
+             S.prog.family ? (", family of " + std::to_string(S.prog.family) + " scenes").c_str() : "",
+             S.compile_ms, S.note.c_str(), rt::spec_compiler().origin.c_str(), S.res.c_str(), S.ready_ms);
     s = b;
-  } else if (c->spec_on && c->uploaded && !c->spec_fits) {
+  } else if (S.level && c->uploaded && !S.prog.fits) {
     snprintf(b, sizeof b, "generic (librt_mi355x.so; scene too large to specialise: > %d objects or > %d leaves)",
              RT_SPEC_MAX_OBJECTS, RT_SPEC_MAX_LEAVES);
     s = b;
-  } else if (c->spec_on && c->uploaded && !c->spec_jobs.empty()) {
+  } else if (S.level && c->uploaded && S.pending) {
     s = "generic (librt_mi355x.so; the scene-specialised program is compiling in the background)";
-  } else if (c->spec_on && c->uploaded && !c->spec_error.empty()) {
-    s = "generic (librt_mi355x.so; specialisation failed: " + c->spec_error + ")";
+  } else if (S.level && c->uploaded && !S.error.empty()) {
+    s = "generic (librt_mi355x.so; specialisation failed: " + S.error + ")";
   } else {
     s = "generic (librt_mi355x.so)";
   }
@@ -310,7 +310,7 @@ int rt_ctx_spec_wait(rt_ctx* c, int32_t timeout_ms) {
   RT_HIP(hipSetDevice(c->device));
   const int rc = rt::spec_wait(c, (double)timeout_ms);
   if (rc == RT_PENDING) return RT_PENDING;
-  if (!c->spec_error.empty()) return fail(RT_ERR_UNSUPPORTED, "%s", c->spec_error.c_str());
+  if (!c->spec.error.empty()) return fail(RT_ERR_UNSUPPORTED, "%s", c->spec.error.c_str());
   return RT_OK;
 }
 
@@ -318,9 +318,9 @@ int rt_ctx_spec_wait_samples(rt_ctx* c, int32_t timeout_ms) {
   if (!c) return fail(RT_ERR_INVALID, "null context");
   RT_HIP(hipSetDevice(c->device));
   if (rt::spec_samples_wait(c, (double)timeout_ms) == RT_PENDING) return RT_PENDING;
-  for (int k = 0; k < 2; ++k)
-    if (!c->samp_error[k].empty())
-      return fail(RT_ERR_UNSUPPORTED, "%s: %s", k == rt::RT_SAMPLE_POINTS ? "rt_spec_points" : "rt_spec_aa", c->samp_error[k].c_str());
+  for (int kind = 0; kind < rt::SPEC_KINDS; ++kind)
+    if (rt::spec_is_sample(kind) && !c->spec.slots[kind][0][0].error.empty())
+      return fail(RT_ERR_UNSUPPORTED, "%s: %s", rt::spec_kind(kind).name, c->spec.slots[kind][0][0].error.c_str());
   return RT_OK;
 }
 
@@ -348,19 +348,19 @@ int rt_ctx_set_option(rt_ctx* c, int32_t option, int32_t value) {
   }
   if (option == RT_OPT_SPECIALIZE) {
     if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "RT_OPT_SPECIALIZE value %d", value);
-    const bool retry = value == c->spec_on && !c->spec_error.empty();   // the same value again: compile again
-    if (value == c->spec_on && !retry) return RT_OK;
+    const bool retry = value == c->spec.level && !c->spec.error.empty();   // the same value again: compile again
+    if (value == c->spec.level && !retry) return RT_OK;
     RT_HIP(hipSetDevice(c->device));
     int rc = rt::wait_launches(c);              // this context's launches in flight may still run the modules
     if (rc) return rc;
     rt::spec_drop(c);
-    c->spec_on = value;
+    c->spec.level = value;
     if (c->uploaded) rt::spec_prepare(c, retry);   // a scene family registered since the upload may hold it
     return RT_OK;
   }
   if (option == RT_OPT_SPEC_SAMPLES) {
     if (value != 0 && value != 1) return fail(RT_ERR_INVALID, "RT_OPT_SPEC_SAMPLES value %d", value);
-    c->samp_on = value;                  // loaded kernels stay: the points / AA calls just stop (or start) taking them
+    c->spec.samples = value;                  // loaded kernels stay: the points / AA calls just stop (or start) taking them
     return RT_OK;
   }
   if (option == RT_OPT_TILE_MASKS) {

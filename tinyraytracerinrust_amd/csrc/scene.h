@@ -19,6 +19,11 @@ namespace rt {
 // `return fail(RT_ERR_INVALID, "...")`.
 int fail(int status, const char* fmt, ...);
 void set_error_message(const std::string& msg);
+#define RT_TRY(call)                                                                   \
+  do {                                                                                 \
+    const int rc_ = (call);                                                            \
+    if (rc_) return rc_;                                                               \
+  } while (0)
 
 enum ShapeKind : int32_t { SHAPE_SPHERE = 0, SHAPE_PLANE = 1, SHAPE_CUBE = 2, SHAPE_CSG = 3 };
 

@@ -3,7 +3,7 @@
 Without arguments: the anti-aliasing pass on the 1080p and 4K globes frames through the package.
 
 --ab: an interleaved A/B in ONE process of RT_OPT_SPEC_SAMPLES 0 and 1 (the generic and the scene-specialised
-sample kernels, spec.hip rt_spec_points / rt_spec_aa) and, with --parent LIB, of another build of the library
+sample kernels, spec_text.cpp rt_spec_points / rt_spec_aa) and, with --parent LIB, of another build of the library
 (one without the option: the parent commit's), each variant through its own ctypes handle, context and upload
 as tools/ab_libs.py does.  Per round every variant runs one anti-aliasing pass of the config's frame (wall time
 with a device synchronisation, and the pass's kernel span from rt_ctx_last_kernel_ms) and --point-launches

@@ -1,4 +1,4 @@
-"""Load / wait listing of the scene-specialised kernels' assembly (csrc/spec.hip): compiles a scene's
+"""Load / wait listing of the scene-specialised kernels' assembly (csrc/spec_text.cpp): compiles a scene's
 program offline as tools/spec_resources.py does, with -S, and prints per kernel its resource line and
 every scalar load, global (vector) load and s_waitcnt of the function body with its line number in the
 body -- the yardstick of the prologue, light-loop and epilogue memory trips (DESIGN.md "Dispatch records").
@@ -44,7 +44,7 @@ def main():
             continue
         label = kname
         src, asm = os.path.join(out, kname + ".hip"), os.path.join(out, kname + ".s")
-        if os.environ.get("NM"):           # the mask-free megakernel (spec.hip kind 3): RT_TILE_MASKS 0, a null table
+        if os.environ.get("NM"):           # the mask-free megakernel (spec_text.cpp SPEC_ROWS_NOMASK): RT_TILE_MASKS 0, a null table
             kname += "_nm"
             k = "#define RT_TILE_MASKS 0\n" + k.replace("s_frames, masks", "s_frames, nullptr")
             src, asm = os.path.join(out, kname + ".hip"), os.path.join(out, kname + ".s")

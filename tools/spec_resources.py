@@ -1,5 +1,5 @@
-"""Offline register / scratch report of the scene-specialised kernels (csrc/spec.hip): dumps the
-program rt_scene_spec_program returns for a scene, splits it into one file per kernel (as spec.hip
+"""Offline register / scratch report of the scene-specialised kernels (csrc/spec_text.cpp): dumps the
+program rt_scene_spec_program returns for a scene, splits it into one file per kernel (as spec_text.cpp
 compiles them), compiles each with hipcc for gfx950 with the hipRTC options and prints the
 compiler's resource-usage remarks (VGPRs, spills, scratch bytes per lane, occupancy, LDS).
 
