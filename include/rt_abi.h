@@ -330,6 +330,14 @@ int rt_ctx_synchronize(rt_ctx* ctx);
  * order are new -- so a wave's prologue is one scalar load where the order entry, the tile division and the
  * mask words were dependent trips; 0: the kernels read the order and the tile-indexed mask table themselves.
  * Same pixels.  rt_ctx_kernel_info says "; tile records: on / off" for the last launch.
+ * RT_OPT_SKY_FILL: 1 (default) a wave of the masked kernels whose dispatch record holds an empty `prim` word --
+ * a sky tile: no primary ray of the tile can hit anything -- stores BLACK for its valid pixels and returns, with
+ * no camera-table load and no trace.  Only programs of scenes whose every object is boxed or is the mask plane
+ * hold the early-out (any other unbounded object keeps its bit in every word), and only launches that read
+ * records take it; the calibrating kernels render every tile.  0: the records mark no tile as sky.  Same pixels.
+ * rt_ctx_kernel_info says "; sky fill: off" or "; sky fill: on (N render, M sky entries)" for the last launch,
+ * ahead of "; last launch: ..." (the counts come from a pinned host word the records' gather fills; the call
+ * never waits, and says "on (counts pending)" until that gather has completed).
  * Two-eye scenes (rt_scene_set_camera_kind) always take the view megakernels (k_stereo.hip: one launch over
  * the tiles of both eyes, mask-free walks): RT_KERNEL_DEFERRED, RT_KERNEL_WAVEFRONT and RT_OPT_TILE_MASKS have
  * no effect on them; RT_OPT_TILE_ORDER and RT_OPT_SPECIALIZE apply (rt_ctx_kernel_info says which kernel ran).
@@ -346,7 +354,7 @@ int rt_ctx_synchronize(rt_ctx* ctx);
 typedef enum rt_option {
   RT_OPT_KERNEL = 0, RT_OPT_TIMING = 1, RT_OPT_TILE_ORDER = 2, RT_OPT_FAST_CLAMP = 3, RT_OPT_WAVEFRONT_CAP = 4,
   RT_OPT_WAVEFRONT_PAIRS = 5, RT_OPT_SPECIALIZE = 6, RT_OPT_TILE_MASKS = 8, RT_OPT_SPEC_SAMPLES = 9,
-  RT_OPT_TILE_RECORDS = 10
+  RT_OPT_TILE_RECORDS = 10, RT_OPT_SKY_FILL = 11
 } rt_option;
 typedef enum rt_kernel_choice {
   RT_KERNEL_AUTO = 0, RT_KERNEL_MEGA = 1, RT_KERNEL_DEFERRED = 2, RT_KERNEL_WAVEFRONT = 3

@@ -30,6 +30,7 @@ RT_OPT_SPECIALIZE = 6
 RT_OPT_TILE_MASKS = 8
 RT_OPT_SPEC_SAMPLES = 9
 RT_OPT_TILE_RECORDS = 10
+RT_OPT_SKY_FILL = 11
 RT_TILEMASK_WORDS = 6     # per tile: prim, shadow[0..3], refl
 RT_KERNEL_AUTO, RT_KERNEL_MEGA, RT_KERNEL_DEFERRED, RT_KERNEL_WAVEFRONT = 0, 1, 2, 3
 RT_CAMERA_PERSPECTIVE, RT_CAMERA_STEREOSCOPIC, RT_CAMERA_ANAGLYPH = 0, 1, 2

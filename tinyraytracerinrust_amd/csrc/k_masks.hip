@@ -31,19 +31,156 @@ __global__ __launch_bounds__(64) void tile_masks_kernel(const RtTileMaskScene* _
 // (order[e], or e without an order) from the tile-indexed mask table.
 __global__ __launch_bounds__(64) void tile_records_kernel(const uint32_t* __restrict__ masks, const int32_t* __restrict__ order,
                                                           uint32_t n_entries, uint32_t n_tiles, uint32_t tiles_x,
-                                                          RtTileRec* __restrict__ out) {
+                                                          uint32_t keep_bit, RtTileRec* __restrict__ out,
+                                                          uint32_t* __restrict__ n_sky) {
   const uint32_t e = blockIdx.x * 64u + threadIdx.x;
-  if (e >= n_entries) return;
-  const uint32_t tile = order ? (uint32_t)order[e] : e;
-  RtTileRec r;
-  r.x0 = (int32_t)((tile % tiles_x) * RT_TILE_W);
-  r.r0 = (int32_t)((tile / tiles_x) * (64 / RT_TILE_W));
-  for (int k = 0; k < RT_TILEMASK_WORDS; ++k)
-    r.mask[k] = tile < n_tiles ? masks[(size_t)tile * RT_TILEMASK_WORDS + k] : 0xffffffffu;
-  out[e] = r;
+  bool sky = false;
+  if (e < n_entries) {
+    const uint32_t tile = order ? (uint32_t)order[e] : e;
+    RtTileRec r;
+    r.x0 = (int32_t)((tile % tiles_x) * RT_TILE_W);
+    r.r0 = (int32_t)((tile / tiles_x) * (64 / RT_TILE_W));
+    for (int k = 0; k < RT_TILEMASK_WORDS; ++k)
+      r.mask[k] = tile < n_tiles ? masks[(size_t)tile * RT_TILEMASK_WORDS + k] : 0xffffffffu;
+    // A record whose prim word is 0 is a sky tile to the kernels (rt_device.h rows_entry).  RT_OPT_SKY_FILL 0:
+    // no record says so -- an empty prim word gets the mask plane's bit, which no walk reads (the plane's
+    // node ignores the mask) and which only ever makes a word looser.
+    if (r.mask[0] == 0) r.mask[0] = keep_bit;
+    sky = r.mask[0] == 0;
+    out[e] = r;
+  }
+  const unsigned long long b = __ballot(sky);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_sky, (uint32_t)__popcll(b));
 }
 
 bool finite3(const double* p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
+
+// ---- tighter bounds of an object's accepted hits (rt_tilemask.h "vertex sets" and "ball")
+// The inverse of the 3x3 part of a leaf's inverse transform, in long double as scene.cpp leaf_box has it.
+bool invert3(const double* M, long double Ai[3][3]) {
+  long double A[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) A[i][j] = M[4 * i + j];
+  const long double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+                          A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+  if (!(fabsl(det) > 1e-300L) || !std::isfinite((double)det)) return false;
+  Ai[0][0] = (A[1][1] * A[2][2] - A[1][2] * A[2][1]) / det;
+  Ai[0][1] = (A[0][2] * A[2][1] - A[0][1] * A[2][2]) / det;
+  Ai[0][2] = (A[0][1] * A[1][2] - A[0][2] * A[1][1]) / det;
+  Ai[1][0] = (A[1][2] * A[2][0] - A[1][0] * A[2][2]) / det;
+  Ai[1][1] = (A[0][0] * A[2][2] - A[0][2] * A[2][0]) / det;
+  Ai[1][2] = (A[0][2] * A[1][0] - A[0][0] * A[1][2]) / det;
+  Ai[2][0] = (A[1][0] * A[2][1] - A[1][1] * A[2][0]) / det;
+  Ai[2][1] = (A[0][1] * A[2][0] - A[0][0] * A[2][1]) / det;
+  Ai[2][2] = (A[0][0] * A[1][1] - A[0][1] * A[1][0]) / det;
+  return true;
+}
+
+// The world point the leaf's inverse transform takes to the local point q.  False unless it is finite, within
+// the culling range, and M w + b gives q back within a quarter of scene.cpp obb()'s margin: the hull of a
+// box's 8 such points then still holds the box with three quarters of the margin, a hundred times the
+// rounding the margin was sized for.
+bool to_world(const double* M, const long double Ai[3][3], const double q[3], double w[3]) {
+  long double c[3];
+  for (int i = 0; i < 3; ++i) c[i] = (long double)q[i] - M[4 * i + 3];
+  for (int i = 0; i < 3; ++i) {
+    w[i] = (double)(Ai[i][0] * c[0] + Ai[i][1] * c[1] + Ai[i][2] * c[2]);
+    if (!(fabs(w[i]) <= RT_CULL_COORD_MAX)) return false;
+  }
+  for (int i = 0; i < 3; ++i) {
+    const double back = M[4 * i] * w[0] + M[4 * i + 1] * w[1] + M[4 * i + 2] * w[2] + M[4 * i + 3];
+    const double mi = fabs(M[4 * i]) + fabs(M[4 * i + 1]) + fabs(M[4 * i + 2]);
+    if (!(fabs(back - q[i]) <= 2.5e-7 * (1.0 + mi))) return false;
+  }
+  return true;
+}
+
+bool box_to_world(const double* M, const long double Ai[3][3], const double lo[3], const double hi[3], double W[8][3]) {
+  for (int k = 0; k < 8; ++k) {
+    const double q[3] = {k & 1 ? hi[0] : lo[0], k & 2 ? hi[1] : lo[1], k & 4 ? hi[2] : lo[2]};
+    if (!to_world(M, Ai, q, W[k])) return false;
+  }
+  return true;
+}
+
+// Object o's vertex sets and ball.  Every leaf scene.cpp obb() would accept as required (one test,
+// rt::required_leaf_box) bounds all accepted hits by its inflated local box, taken to world space as 8
+// corners; each box is first cut down, in its own frame, to the extent the other required leaves' world
+// corners have there (hits lie in every one of those hulls; 1e-9 relative for the transform's rounding) --
+// globes.scene's rods are a thin long sphere inside a cube: 2 x 200 x 2 becomes 2 x 40 x 2.  A required sphere
+// leaf whose transform is a similarity (rows orthogonal and of one length within 1e-9) also gives a ball:
+// |M p + b - c| <= r_eps means |p - centre| <= r_eps / scale.
+void object_bounds(const rt::FlatScene& f, const RtObject& ob, int o, RtTileMaskScene* t, int* n_sets) {
+  struct Req {
+    const RtLeaf* R;
+    long double Ai[3][3];
+    double lo[3], hi[3], W[8][3];
+  };
+  std::vector<Req> req;
+  for (int32_t r = ob.leaf_begin; r < ob.leaf_begin + ob.leaf_count && req.size() < RT_TILEMASK_OBJ_SETS; ++r) {
+    Req q;
+    double det;
+    q.R = &f.leaves[(size_t)r];
+    if (!rt::required_leaf_box(f, ob, r, q.lo, q.hi, &det) || !invert3(q.R->inv, q.Ai)) continue;
+    if (!box_to_world(q.R->inv, q.Ai, q.lo, q.hi, q.W)) continue;
+    req.push_back(q);
+  }
+  double best_r2 = INFINITY;
+  for (size_t a = 0; a < req.size(); ++a) {
+    const Req& q = req[a];
+    const double* M = q.R->inv;
+    // ---- the ball
+    if (q.R->kind == RT_N_SPHERE) {
+      double G[3][3], w[3];
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) G[i][j] = M[4 * i] * M[4 * j] + M[4 * i + 1] * M[4 * j + 1] + M[4 * i + 2] * M[4 * j + 2];
+      const double s2 = (G[0][0] + G[1][1] + G[2][2]) / 3.0;
+      bool sim = std::isfinite(s2) && s2 > 1e-200 && s2 < 1e200;
+      for (int i = 0; i < 3 && sim; ++i)
+        for (int j = 0; j < 3 && sim; ++j) sim = fabs(G[i][j] - (i == j ? s2 : 0.0)) <= 1e-9 * s2;
+      if (sim && to_world(M, q.Ai, q.R->c, w)) {
+        double rl = 0.0;                                    // r_eps plus obb()'s margin, the widest axis
+        for (int i = 0; i < 3; ++i) rl = fmax(rl, 0.5 * (q.hi[i] - q.lo[i]));
+        const double wmax = fmax(fmax(fabs(w[0]), fabs(w[1])), fabs(w[2]));
+        const double rw = rl / sqrt(s2) * (1.0 + 1e-6) + 1e-6 * (1.0 + wmax), r2 = rw * rw;
+        if (std::isfinite(r2) && r2 < best_r2) {
+          best_r2 = r2;
+          for (int i = 0; i < 3; ++i) t->ball[o][i] = w[i];
+          t->ball[o][3] = r2;
+          t->balled |= 1u << o;
+        }
+      }
+    }
+    // ---- the vertex set: the leaf's box cut down to the others' extent in its frame
+    if (*n_sets >= RT_TILEMASK_SETS) continue;
+    double lo[3], hi[3];
+    bool ok = true;
+    for (int i = 0; i < 3; ++i) { lo[i] = q.lo[i]; hi[i] = q.hi[i]; }
+    for (size_t b = 0; b < req.size() && ok; ++b) {
+      if (b == a) continue;
+      for (int i = 0; i < 3 && ok; ++i) {
+        double l = INFINITY, h = -INFINITY;
+        for (int k = 0; k < 8; ++k) {
+          const double* w = req[b].W[k];
+          const double v = M[4 * i] * w[0] + M[4 * i + 1] * w[1] + M[4 * i + 2] * w[2] + M[4 * i + 3];
+          // the transform's rounding, and to_world's residual on the cut face four times over
+          const double m = 1e-9 * (1.0 + fabs(M[4 * i] * w[0]) + fabs(M[4 * i + 1] * w[1]) + fabs(M[4 * i + 2] * w[2]) + fabs(M[4 * i + 3])) +
+                           1e-6 * (1.0 + fabs(M[4 * i]) + fabs(M[4 * i + 1]) + fabs(M[4 * i + 2]));
+          l = fmin(l, v - m);
+          h = fmax(h, v + m);
+          ok = ok && std::isfinite(v) && std::isfinite(m);
+        }
+        lo[i] = fmax(lo[i], l);
+        hi[i] = fmin(hi[i], h);
+        ok = ok && lo[i] <= hi[i];
+      }
+    }
+    double W[8][3];
+    if (!ok || !box_to_world(M, q.Ai, lo, hi, W)) memcpy(W, q.W, sizeof W);      // the uncut box is a bound too
+    memcpy(t->sets[*n_sets], W, sizeof W);
+    ++*n_sets;
+  }
+}
 
 // What the predicate reads of a flattened scene.  valid = 0 (every word all ones) for scenes of more than
 // RT_TILEMASK_OBJECTS objects, frames beyond RT_TILEMASK_MAX_SIDE and non-finite cameras.
@@ -63,6 +200,7 @@ void tilemask_scene(const rt::FlatScene& f, RtTileMaskScene* t) {
     t->n_objects = 0;
     return;
   }
+  int n_sets = 0;
   for (size_t o = 0; o < f.objects.size(); ++o) {
     const RtObject& ob = f.objects[o];
     bool boxed = ob.cull == RT_CULL_BOX;
@@ -72,7 +210,10 @@ void tilemask_scene(const rt::FlatScene& f, RtTileMaskScene* t) {
       boxed = boxed && fabs(ob.blo[k]) <= RT_CULL_COORD_MAX && fabs(ob.bhi[k]) <= RT_CULL_COORD_MAX && ob.blo[k] <= ob.bhi[k];
     }
     if (boxed) t->boxed |= 1u << o;
+    t->set_begin[o] = n_sets;
+    if (boxed) object_bounds(f, ob, (int)o, t, &n_sets);
   }
+  for (size_t o = f.objects.size(); o <= RT_TILEMASK_OBJECTS; ++o) t->set_begin[o] = n_sets;
   for (int l = 0; l < t->n_lights && l < RT_TILEMASK_LIGHTS; ++l)
     for (int k = 0; k < 3; ++k) t->light[l][k] = f.lights[(size_t)l].p[k];
   t->plane = rt::tilemask_plane(f);
@@ -101,6 +242,7 @@ void drop_mask(rt_ctx::MaskSlot& s) {
 
 void drop_rec(rt_ctx::RecSlot& s) {
   if (s.d_recs) (void)hipFree(s.d_recs);         // hipFree waits for work that may still read it
+  if (s.h_sky) (void)hipHostFree(s.h_sky);
   if (s.ready) (void)hipEventDestroy(s.ready);
   s = rt_ctx::RecSlot();
 }
@@ -182,6 +324,32 @@ int tilemask_plane(const FlatScene& f) {
   return -1;
 }
 
+// Sky tiles (RT_OPT_SKY_FILL): a tile's prim word can only be 0 -- no primary ray of the tile hits anything,
+// every pixel BLACK -- when every object is boxed or is the mask plane (an unbounded object keeps its bit);
+// the specialised programs compile the early-out in for such scenes only (spec_text.cpp SKY_OK).
+bool tilemask_sky_ok(const FlatScene& f) {
+  const int plane = tilemask_plane(f);
+  if (plane < 0) return false;
+  for (size_t o = 0; o < f.objects.size(); ++o)
+    if ((int)o != plane && f.objects[o].cull != RT_CULL_BOX) return false;
+  return true;
+}
+
+// rt_scene_describe's lines on the tile masks' bounds: per boxed object its vertex sets and whether it has a ball
+std::string describe_tile_bounds(const FlatScene& f) {
+  RtTileMaskScene t;
+  tilemask_scene(f, &t);
+  std::string s;
+  char buf[128];
+  for (int o = 0; o < t.n_objects; ++o) {
+    if (!((t.boxed >> o) & 1u)) continue;
+    snprintf(buf, sizeof buf, "tile-mask bounds object %d: sets %d ball %d\n", o, t.set_begin[o + 1] - t.set_begin[o],
+             (int)((t.balled >> o) & 1u));
+    s += buf;
+  }
+  return s;
+}
+
 size_t put_mask_scene(const FlatScene& f, std::vector<uint8_t>& blob, bool* ok) {
   RtTileMaskScene t;
   tilemask_scene(f, &t);
@@ -211,12 +379,14 @@ int launch_masks(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size
 // else gathered on st, behind the mask fill: launch_masks has put the fill, or a wait for its event, on st
 // already.  Launches on other streams wait for the gather's own event.
 int launch_records(rt_ctx* c, hipStream_t st, const void* mask_slot, const int32_t* d_order, uint64_t order_id,
-                   uint32_t n_entries, const RtTileRec** table) {
+                   uint32_t n_entries, const RtTileRec** table, const void** rslot) {
   const rt_ctx::MaskSlot* ms = (const rt_ctx::MaskSlot*)mask_slot;
   *table = nullptr;
+  if (rslot) *rslot = nullptr;
+  const bool sky_fill = c->sky_fill && c->sky_ok;
   rt_ctx::RecSlot* slot = nullptr;
   for (auto& s : c->recs)
-    if (s.valid && s.fill_id == ms->fill_id && s.order_id == order_id && s.n_entries == n_entries) slot = &s;
+    if (s.valid && s.fill_id == ms->fill_id && s.order_id == order_id && s.n_entries == n_entries && s.sky_fill == sky_fill) slot = &s;
   if (!slot) {
     slot = &c->recs[0];
     for (auto& s : c->recs) {
@@ -224,15 +394,24 @@ int launch_records(rt_ctx* c, hipStream_t st, const void* mask_slot, const int32
       if (s.last_use < slot->last_use) slot = &s;
     }
     drop_rec(*slot);
-    RT_HIP(hipMalloc((void**)&slot->d_recs, (size_t)n_entries * sizeof(RtTileRec)));
+    // (one more record's room behind the table: the count of sky entries, for rt_ctx_kernel_info)
+    RT_HIP(hipMalloc((void**)&slot->d_recs, ((size_t)n_entries + 1) * sizeof(RtTileRec)));
+    slot->d_sky = (uint32_t*)(slot->d_recs + n_entries);
+    RT_HIP(hipMemsetAsync(slot->d_sky, 0, sizeof(uint32_t), st));
+    RT_HIP(hipHostMalloc((void**)&slot->h_sky, sizeof(uint32_t), hipHostMallocDefault));
+    *slot->h_sky = 0;
+    slot->rec_id = ++c->rec_ids;
+    slot->sky_fill = sky_fill;
     RT_HIP(hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming));
     slot->order_id = order_id;
     slot->fill_id = ms->fill_id;
     slot->n_entries = n_entries;
     const uint32_t tiles_x = (uint32_t)((c->dev.width + RT_TILE_W - 1) / RT_TILE_W);
     hipLaunchKernelGGL(tile_records_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, st, (const uint32_t*)ms->d_masks, d_order,
-                       n_entries, (uint32_t)ms->n_tiles, tiles_x, slot->d_recs);
+                       n_entries, (uint32_t)ms->n_tiles, tiles_x,
+                       sky_fill || c->mask_plane < 0 ? 0u : 1u << c->mask_plane, slot->d_recs, slot->d_sky);
     RT_HIP(hipGetLastError());
+    RT_HIP(hipMemcpyAsync(slot->h_sky, slot->d_sky, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     RT_HIP(hipEventRecord(slot->ready, st));
     slot->fill_stream = st;
     slot->valid = true;
@@ -247,7 +426,23 @@ int launch_records(rt_ctx* c, hipStream_t st, const void* mask_slot, const int32
     }
   }
   *table = slot->d_recs;
+  if (rslot) *rslot = slot;
   return RT_OK;
+}
+
+uint64_t record_id(const void* rslot) { return rslot ? ((const rt_ctx::RecSlot*)rslot)->rec_id : 0; }
+
+// The sky entries among a record table's (rt_ctx_kernel_info): the pinned word the gather's stream copied the
+// count to, read once the gather's event has completed -- no wait, no stream touched.
+int64_t record_sky_entries(rt_ctx* c, const void* rslot, uint64_t rec_id, uint32_t* n_entries) {
+  const rt_ctx::RecSlot* slot = (const rt_ctx::RecSlot*)rslot;
+  if (!slot || !slot->valid || slot->rec_id != rec_id) return -1;
+  if (!slot->seen_ready && hipEventQuery(slot->ready) != hipSuccess) {
+    (void)hipGetLastError();
+    return -2;
+  }
+  *n_entries = slot->n_entries;
+  return (int64_t)*slot->h_sky;
 }
 
 }  // namespace rt

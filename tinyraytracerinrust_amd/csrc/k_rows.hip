@@ -204,6 +204,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   // reports the render kernel alone.  (The kernel choice below is restated for it.)
   const uint32_t* mask_table = nullptr;
   const void* mask_slot = nullptr;
+  const void* rec_slot = nullptr;
   const RtTileRec* rec_table = nullptr;       // the launch's dispatch records (RT_OPT_TILE_RECORDS), gathered from both
   const rt::SpecProgram& sp = c->spec.prog;
   if (c->spec.loaded && !refr && sp.mode == RT_MODE_REFL && !sp.family && c->dev.n_objects <= 32 &&
@@ -217,7 +218,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
       RT_TRY(launch_masks(c, st, a0, a1, a2, a3, n_tiles, &mask_table, &mask_slot));
     // (a deferred slot's entries carry split parts: no plain tiles to gather)
     if (mask_table && c->tile_records && !(order && slot->deferred))
-      RT_TRY(launch_records(c, st, mask_slot, order, order ? slot->order_id : 0, grid.x, &rec_table));
+      RT_TRY(launch_records(c, st, mask_slot, order, order ? slot->order_id : 0, grid.x, &rec_table, &rec_slot));
   }
   if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
   // the row kernels carry the context's completion event for this stream as their stop event
@@ -292,6 +293,10 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   c->last_masked = masks != nullptr;
   const RtTileRec* recs = masks ? rec_table : nullptr;
   c->last_records = recs != nullptr;
+  // (a calibrating kernel renders every tile: cost[tile] is a tile's full time)
+  const bool sky = recs && !calibrate && c->sky_fill && c->sky_ok;
+  c->last_sky_slot = sky ? rec_slot : nullptr;
+  c->last_sky_id = sky ? rt::record_id(rec_slot) : 0;
   // a megakernel launch without a table runs the program's mask-free megakernel (SPEC_ROWS_NOMASK)
   if (sfn && !prim && !deferred && !masks && spec_fn(c, SPEC_ROWS_NOMASK, f64, calibrate))
     sfn = spec_fn(c, SPEC_ROWS_NOMASK, f64, calibrate);

@@ -49,7 +49,9 @@ using __hip_internal::uint64_t;
 // Dispatch record of one order entry of a masked launch (k_masks.hip tile_records_kernel; rt_device.h
 // rows_entry reads it with one 32-byte scalar load): the entry's tile as its first column and first output
 // row (no division in the kernel) and the tile's mask words.  A calibrating launch has no order: its entry e
-// is tile e, so the record holds no tile index.  Entry e's record is records[e]: four consecutive workgroups
+// is tile e, so the record holds no tile index.  An empty prim word (mask[0] == 0) marks a sky tile: the wave
+// stores BLACK and returns (RT_OPT_SKY_FILL; with the option off the gather leaves no prim word empty).
+// Entry e's record is records[e]: four consecutive workgroups
 // share a 128-byte line.  (A layout that gives each XCD's workgroups -- e, e + 8, ... -- a contiguous run was
 // measured equal, DESIGN.md section 7, and cost the kernel an argument and a multiply.)
 struct alignas(32) RtTileRec {

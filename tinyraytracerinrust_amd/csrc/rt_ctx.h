@@ -104,6 +104,10 @@ struct rt_ctx {
     uint64_t order_id = 0;            // the order gathered from (0: the identity)
     uint64_t fill_id = 0;             // the mask fill gathered from
     RtTileRec* d_recs = nullptr;
+    uint32_t* d_sky = nullptr;        // behind the table: how many records say sky, copied on the gather's stream
+    uint32_t* h_sky = nullptr;        //   to this pinned host word ahead of `ready` (rt_ctx_kernel_info reads it
+    uint64_t rec_id = 0;              //   once hipEventQuery says so, never waiting); rec_id: never reused
+    bool sky_fill = false;            // gathered with RT_OPT_SKY_FILL on for a scene that can have sky tiles
     uint32_t n_entries = 0;           // order entries = records
     uint64_t last_use = 0;
     hipStream_t fill_stream = nullptr;
@@ -116,6 +120,14 @@ struct rt_ctx {
   uint64_t mask_fills = 0, order_ids = 0;   // count mask fills and calibrations: MaskSlot::fill_id, OrderSlot::order_id
   bool tile_records = true;             // rt_ctx_set_option(RT_OPT_TILE_RECORDS)
   bool last_records = false;            // the last row launch passed a record table (rt_ctx_kernel_info)
+  // Sky tiles (rt_ctx_set_option(RT_OPT_SKY_FILL), rt_device.h rows_entry): a record whose prim word is 0
+  // makes its wave store BLACK and return.  sky_ok, mask_plane: the uploaded scene's (k_masks.hip
+  // tilemask_sky_ok, tilemask_plane); last_sky_*: the last row launch's record table, where it can say sky.
+  bool sky_fill = true;
+  bool sky_ok = false;
+  int mask_plane = -1;
+  const void* last_sky_slot = nullptr;
+  uint64_t last_sky_id = 0, rec_ids = 0;
   int tile_masks = 1;                   // rt_ctx_set_option(RT_OPT_TILE_MASKS): 0 never, 1 where they pay (OrderSlot::masks_pay), 2 always
   bool masks_ok = false;                // the uploaded scene has a mask scene in its blob (<= 32 objects)
   const void* d_mask_scene = nullptr;   // RtTileMaskScene in the blob
@@ -186,8 +198,12 @@ int launch_masks(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size
 // The dispatch records (RecSlot) of a launch of n_entries order entries (d_order of calibration order_id; null and
 // 0: the identity) whose mask table is mask_slot's, gathered on st first if the masks or the order are new.
 int launch_records(rt_ctx* c, hipStream_t st, const void* mask_slot, const int32_t* d_order, uint64_t order_id,
-                   uint32_t n_entries, const RtTileRec** table);
+                   uint32_t n_entries, const RtTileRec** table, const void** rslot = nullptr);
 void drop_records(rt_ctx* c);                  // every record table (upload, free)
+// How many of a record table's entries say sky (rslot as launch_records gave it, rec_id its RecSlot::rec_id);
+// -1: the table has been dropped since, -2: its gather has not completed yet.  Never waits.
+int64_t record_sky_entries(rt_ctx* c, const void* rslot, uint64_t rec_id, uint32_t* n_entries);
+uint64_t record_id(const void* rslot);
 size_t put_mask_scene(const FlatScene& f, std::vector<uint8_t>& blob, bool* ok);   // appends the RtTileMaskScene
 int ensure_scratch(rt_ctx* c, size_t bytes);   // grow-only device scratch for host-pointer launches
 bool is_device_ptr(const void* p);

@@ -223,6 +223,9 @@ int rt_ctx_upload(rt_ctx* c, const rt_scene* s) {
   d.cam_sy = (const double*)(b + o_csy);
   c->d_mask_scene = b + o_mask;
   c->masks_ok = masks_ok;
+  c->sky_ok = rt::tilemask_sky_ok(f);
+  c->mask_plane = rt::tilemask_plane(f);
+  c->last_sky_slot = nullptr;
   d.n_objects = (int32_t)f.objects.size();
   d.n_lights = (int32_t)f.lights.size();
   d.n_leaves = (int32_t)f.leaves.size();
@@ -298,6 +301,15 @@ int rt_ctx_kernel_info(rt_ctx* c, char* buf, size_t cap) {
   } else {
     s = "generic (librt_mi355x.so)";
   }
+  // sky fill: the last launch's records could say sky; the counts come from a pinned word once the records'
+  // gather has completed (no wait: "counts pending" until then, no counts once the table has been dropped).
+  // (Ahead of "last launch": callers match the text from there to the end.)
+  uint32_t n_entries = 0;
+  const int64_t n_sky = c->last_sky_slot ? rt::record_sky_entries(c, c->last_sky_slot, c->last_sky_id, &n_entries) : -1;
+  if (n_sky >= 0)
+    s += "; sky fill: on (" + std::to_string((int64_t)n_entries - n_sky) + " render, " + std::to_string(n_sky) + " sky entries)";
+  else
+    s += !c->last_sky_slot ? "; sky fill: off" : n_sky == -2 ? "; sky fill: on (counts pending)" : "; sky fill: on";
   s += std::string("; last launch: ") + c->last_kernel;
   s += c->last_masked ? "; tile masks: on" : "; tile masks: off";
   s += c->last_records ? "; tile records: on" : "; tile records: off";
@@ -371,6 +383,11 @@ int rt_ctx_set_option(rt_ctx* c, int32_t option, int32_t value) {
   if (option == RT_OPT_TILE_RECORDS) {
     if (value != 0 && value != 1) return fail(RT_ERR_INVALID, "RT_OPT_TILE_RECORDS value %d", value);
     c->tile_records = value != 0;        // the tables stay: launches just stop (or start) passing them
+    return RT_OK;
+  }
+  if (option == RT_OPT_SKY_FILL) {
+    if (value != 0 && value != 1) return fail(RT_ERR_INVALID, "RT_OPT_SKY_FILL value %d", value);
+    c->sky_fill = value != 0;            // record tables are keyed by it: the next launch gathers its own
     return RT_OK;
   }
   if (option == RT_OPT_WAVEFRONT_PAIRS) {

@@ -1888,6 +1888,20 @@ __device__ __forceinline__ void rows_entry(const RtDevScene& S, unsigned entry, 
     x = R->x0 + lane % RT_TILE_W;
     r = R->r0 + lane / RT_TILE_W;
     for (int k = 0; k < RT_TILEMASK_WORDS; ++k) tm.w[k] = R->mask[k];
+#if defined(RT_SPEC) && RT_TILE_MASKS
+    // A sky tile (RT_OPT_SKY_FILL): the record's prim word is empty -- no boxed object in the tile's cone, and
+    // the mask plane's own bit cleared because no ray of the tile can meet it; SKY_OK: the scene has no other
+    // unbounded object -- so every valid pixel is BLACK (Color::BLACK, alpha as store_pixel writes it).  The
+    // same guards and store as below; no camera-table load, no trace.  At kernel entry, not around the walks.
+    // The calibrating kernels render every tile (cost[tile] stays a tile's full time).
+    if constexpr (rt_spec::SKY_OK && !CAL)
+      if (tm.w[0] == 0) {
+        if (x >= S.width || r >= n_rows) return;
+        if (band_row(r, y_first, band_rows, band_pitch, n_rows) >= S.height) return;
+        store_pixel<F64, PRIM>(out + (size_t)r * stride, x, Col{0.0, 0.0, 0.0}, rgb);
+        return;
+      }
+#endif
   } else {
     tile = CAL || !order ? entry : (unsigned)order[entry];
     tile_pixel(tile, lane, S.width, &x, &r);

@@ -12,9 +12,10 @@
 // Per tile RT_TILEMASK_WORDS 32-bit words: prim, shadow[0..3], refl; bit o = object o (the specialised
 // programs have at most 32 objects); a word the predicate computed holds no bit beyond the scene's
 // objects, a word it gave up on is 0xffffffff.  A bit may be 0 ONLY IF no ray of that class from any
-// pixel of the tile can have an accepted hit inside object o's culling box blo/bhi -- then skipping the
-// object changes no accepted hit, and the pixels are bit-identical.  Objects without a finite box keep
-// their bit (but for the mask plane's own bit in `prim`, see below).
+// pixel of the tile can have an accepted hit of object o, all of which lie inside its culling box
+// blo/bhi and inside every further bound below -- then skipping the object changes no accepted hit, and
+// the pixels are bit-identical.  Objects without a finite box keep their bit (but for the mask plane's
+// own bit in `prim`, see below).
 //
 // Why a cleared bit is safe (the argument, in the style of the f32-culling comment in rt_device.h):
 //  * camera_ray is LINEAR in (sx, sy) and not normalised, so the primary rays of the tile's pixels
@@ -41,14 +42,42 @@
 //    conv(Q u {L}).  An object is out when its 8 box corners are all outside one of the four planes
 //    through L and an edge of Q, all on the far side of the mask plane from L, all beyond the plane
 //    through L parallel to the mask plane, or its box is disjoint from the AABB of Q u {L}.  The
-//    pyramid is bounded, so a box rising above the light needs no special case.
+//    pyramid is bounded, so a box rising above the light needs no special case -- but a side plane is an
+//    infinite plane through L, and a box that rises above L crosses it beyond the apex, at any distance
+//    to the side.  The pyramid lies on the floor's side of the plane through L parallel to the mask
+//    plane, so the side planes are asked only about the part of each bound on that side (tm_clip_outside:
+//    the corners inside and the points where edges cross, a convex polytope's vertices; its comment has
+//    the tolerances: corners 1e-12, crossing points 1e-7 of the dot product's magnitude, the clip itself
+//    only ever looser).  Nothing left on that side: out.
+//  * vertex sets (k_masks.hip object_bounds): beside the world box an object has up to
+//    RT_TILEMASK_OBJ_SETS sets of 8 world-space corners, one per leaf R that scene.cpp obb() accepts as
+//    required (R is a sphere or cube and every other leaf's filter holds the literal 2R+1: a hit of R
+//    lies on R, any other accepted hit passed R's is_inside; rt::required_leaf_box is obb()'s own test).
+//    Each is R's box in R's frame with obb()'s margins (>= 1e-6 (1 + |M_i| + |T_i|) per axis, a hundred
+//    times the rounding of q = M p + b for |p| <= 1e6), cut to the extent the other required leaves'
+//    corners have in that frame (hits lie in all of those hulls; every cut face is moved out again by the
+//    same margin), and taken to world space through the inverse of R.inv computed in long double.  A
+//    corner is kept only if R.inv takes it back to its local point within a quarter of the margin, so
+//    the hull of the 8 holds the local box with three quarters of it; a singular or non-finite
+//    transform, or a corner beyond RT_CULL_COORD_MAX, drops the set.  The corners form an affine image of
+//    a box, so corner k's edge neighbours are k^1, k^2, k^4 (rounding bends a face by < 1e-15 relative,
+//    inside every tolerance).  An object is outside a half-space when ANY of its bounds is wholly
+//    outside, since every bound holds all accepted hits; the world box is tried first.
+//  * ball: a required sphere leaf whose transform is a similarity (M M^T = s^2 I within 1e-9) bounds the
+//    hits by the world ball |p - centre| <= r_eps / s.  The radius takes obb()'s margin, 1e-6 relative
+//    (a thousand times the similarity's tolerance) and 1e-6 (1 + |centre|) absolute; the centre passes
+//    the same round trip as a corner.  One ball per object, the smallest.  Outside: the centre's signed
+//    distance below -radius, compared as squares with 1e-9 to spare (tm_ball_outside).  At the shadow
+//    side planes the ball is clipped at the light too (tm_ball_outside_clipped: the largest value of a
+//    linear function over a ball cut by a plane, in closed form; its comment has the cases).
 //  * refl: reflect_dir mirrors the direction in the plane's unit normal, so the reflection ray of a hit
 //    p is the ray from the mirrored camera centre C' through p, beyond p.  An object is out when its
-//    corners are all outside one side plane through C' and an edge of Q, or all on C's far side of the
-//    plane.  Taken only when RtObject::nunit is parallel to the world plane's normal within 1e-12 (the
-//    reference builds a transformed normal separately from the inverse; a rotation's "inverse" is not a
-//    true one): otherwise all ones.
-//  * everything above is proven for |coordinates| <= RT_CULL_COORD_MAX (camera, lights, boxes, Q) and
+//    bounds are outside one side plane through C' and an edge of Q, or on C's far side of the plane
+//    (not clipped: a clip at the mask plane would cut nothing off objects that stand on the floor).
+//    Taken only when RtObject::nunit is parallel to the world plane's normal within 1e-12 (the reference
+//    builds a transformed normal separately from the inverse; a rotation's "inverse" is not a true one):
+//    otherwise all ones.
+//  * everything above is proven for |coordinates| <= RT_CULL_COORD_MAX (camera, lights, boxes, sets, Q) and
 //    frames up to 65 536 pixels a side.  Outside that range, with a non-finite value anywhere, more
 //    than 4 lights, no mask plane, or a cone whose corner directions are not in convex position (a
 //    degenerate camera; the only camera type of this renderer is the perspective one), the class is
@@ -74,6 +103,8 @@
 #define RT_TILEMASK_LIGHTS 4
 #define RT_TILEMASK_OBJECTS 32
 #define RT_TILEMASK_MAX_SIDE 65536
+#define RT_TILEMASK_OBJ_SETS 4       // vertex sets per object
+#define RT_TILEMASK_SETS 64          // ... and per scene (12 KiB): later objects go without
 
 // What the predicate reads of a scene (host: tilemask_scene in k_masks.hip; the device copy lives in
 // the scene blob).
@@ -89,6 +120,13 @@ struct RtTileMaskScene {
   double pn[3], pd;                  // the mask plane in world space: pn . x + pd = 0
   double blo[RT_TILEMASK_OBJECTS][3], bhi[RT_TILEMASK_OBJECTS][3];
   double light[RT_TILEMASK_LIGHTS][3];
+  // Tighter bounds of a boxed object's accepted hits (see "vertex sets" above): object o's sets are
+  // sets[set_begin[o] .. set_begin[o + 1]), at most RT_TILEMASK_OBJ_SETS each; ball[o] = centre and
+  // squared radius where bit o of `balled` is set.
+  uint32_t balled;
+  int32_t set_begin[RT_TILEMASK_OBJECTS + 1];
+  double ball[RT_TILEMASK_OBJECTS][4];
+  double sets[RT_TILEMASK_SETS][8][3];   // corner k's neighbours along the box's edges are k^1, k^2, k^4
 };
 
 struct TmV { double x, y, z; };
@@ -113,6 +151,121 @@ RT_TM_HD bool tm_all_outside(TmV n, TmV apex, const double* lo, const double* hi
   return true;
 }
 
+// The signed value n . (c - apex) of a point and the magnitude its tolerance is taken of; `a` bounds |c|
+// per coordinate (|c| itself for a corner, the larger endpoint for a point on an edge).
+RT_TM_HD bool tm_pt_outside(TmV n, TmV apex, TmV c, TmV a, double tol) {
+  const double s = tm_dot(n, tm_sub(c, apex));
+  const double mag = fabs(n.x) * (a.x + fabs(apex.x)) + fabs(n.y) * (a.y + fabs(apex.y)) + fabs(n.z) * (a.z + fabs(apex.z));
+  return s < -tol * mag;
+}
+RT_TM_HD TmV tm_abs(TmV c) { return {fabs(c.x), fabs(c.y), fabs(c.z)}; }
+RT_TM_HD void tm_box_corners(const double* lo, const double* hi, TmV c[8]) {
+  for (int k = 0; k < 8; ++k) c[k] = {k & 1 ? hi[0] : lo[0], k & 2 ? hi[1] : lo[1], k & 4 ? hi[2] : lo[2]};
+}
+
+// tm_all_outside for the part of the box-shaped vertex set c[0..7] (corner k's edge neighbours are
+// k^1, k^2, k^4) inside the half-space cn . (x - cp) >= 0: a convex polytope whose vertices are the
+// corners inside and the points where an edge crosses the clipping plane, so a linear function that is
+// negative on all of those is negative on all of it.  A corner counts as inside unless it is outside by
+// the corner tolerance (NaN: inside), so the clipped part only grows.  A crossing point is
+// c[k] + t (c[j] - c[k]), t = s_k / (s_k - s_j) clamped to [0, 1]: the two signed values carry rounding
+// of <= 1e-15 of `magc`, so where s_k - s_j >= 1e-6 magc the point is off along the edge by < 4e-9 of
+// its length, < 8e-9 of the side test's magnitude, and is tested with 1e-7; an edge flatter to the
+// clipping plane than that is kept whole (its outside corner is tested too).  Nothing inside: outside.
+RT_TM_HD bool tm_clip_outside(const TmV c[8], TmV n, TmV apex, TmV cn, TmV cp) {
+  double s[8];
+  bool in[8];
+  for (int k = 0; k < 8; ++k) {
+    s[k] = tm_dot(cn, tm_sub(c[k], cp));
+    const double mag = fabs(cn.x) * (fabs(c[k].x) + fabs(cp.x)) + fabs(cn.y) * (fabs(c[k].y) + fabs(cp.y)) +
+                       fabs(cn.z) * (fabs(c[k].z) + fabs(cp.z));
+    in[k] = !(s[k] < -1e-12 * mag);
+  }
+  for (int k = 0; k < 8; ++k) {
+    if (!in[k]) continue;
+    if (!tm_pt_outside(n, apex, c[k], tm_abs(c[k]), 1e-12)) return false;
+    for (int b = 1; b < 8; b <<= 1) {
+      const int j = k ^ b;
+      if (in[j]) continue;
+      const TmV a = {fmax(fabs(c[k].x), fabs(c[j].x)), fmax(fabs(c[k].y), fabs(c[j].y)), fmax(fabs(c[k].z), fabs(c[j].z))};
+      const double magc = fabs(cn.x) * (a.x + fabs(cp.x)) + fabs(cn.y) * (a.y + fabs(cp.y)) + fabs(cn.z) * (a.z + fabs(cp.z));
+      const double den = s[k] - s[j];
+      if (!(den >= 1e-6 * magc)) {                         // nearly in the clipping plane (or NaN): the whole edge
+        if (!tm_pt_outside(n, apex, c[j], tm_abs(c[j]), 1e-12)) return false;
+        continue;
+      }
+      double t = s[k] / den;
+      t = t > 0.0 ? (t < 1.0 ? t : 1.0) : 0.0;             // NaN: 0, the corner itself
+      const TmV p = {c[k].x + (c[j].x - c[k].x) * t, c[k].y + (c[j].y - c[k].y) * t, c[k].z + (c[j].z - c[k].z) * t};
+      if (!tm_pt_outside(n, apex, p, a, 1e-7)) return false;
+    }
+  }
+  return true;
+}
+
+// The ball (centre b[0..2], squared radius b[3]) lies strictly outside the half-space n . (x - apex) >= 0:
+// the centre's signed distance is below -radius, compared as squares (no square root: the same bits on
+// host and device) with 1e-9 to spare; NaN answers no.
+RT_TM_HD bool tm_ball_outside(TmV n, TmV apex, const double* b) {
+  const TmV c = {b[0], b[1], b[2]};
+  const double s = tm_dot(n, tm_sub(c, apex));
+  return tm_pt_outside(n, apex, c, tm_abs(c), 1e-12) && s * s > b[3] * tm_dot(n, n) * (1.0 + 1e-9);
+}
+
+// The same for the part of the ball inside the half-space cn . (x - cp) >= 0.  With h = cn . (c - cp) and
+// g = cn . n: the part is empty when h < -r |cn|.  Otherwise n . (x - apex) is largest over the whole ball at
+// c + r n / |n|; where that point lies beyond the clipping plane (h + r g / |n| < 0) the largest value over
+// the part is taken on the disc the plane cuts out of the ball -- centre c' = c - (h / cn.cn) cn, squared
+// radius r^2 - h^2 / cn.cn -- and is n . (c' - apex) + radius |n_t|, n_t = n less its component along cn.
+// Everything is compared as squares, each with 1e-9 to spare on the side that keeps; where the highest
+// point is not clearly beyond the plane only the whole ball is asked (the two bounds meet there).
+RT_TM_HD bool tm_ball_outside_clipped(TmV n, TmV apex, const double* b, TmV cn, TmV cp) {
+  if (tm_ball_outside(n, apex, b)) return true;
+  const TmV c = {b[0], b[1], b[2]};
+  const double N2 = tm_dot(cn, cn), n2 = tm_dot(n, n), h = tm_dot(cn, tm_sub(c, cp)), g = tm_dot(cn, n);
+  if (!(N2 > 0.0 && n2 > 0.0 && b[3] >= 0.0)) return false;
+  const double magh = fabs(cn.x) * (fabs(c.x) + fabs(cp.x)) + fabs(cn.y) * (fabs(c.y) + fabs(cp.y)) + fabs(cn.z) * (fabs(c.z) + fabs(cp.z));
+  const bool below = h < -1e-12 * magh;
+  if (below && h * h > b[3] * N2 * (1.0 + 1e-9)) return true;          // nothing of the ball inside
+  const bool beyond = g >= 0.0 ? below && h * h * n2 > b[3] * g * g * (1.0 + 1e-9)
+                               : below || h * h * n2 * (1.0 + 1e-9) < b[3] * g * g;
+  if (!beyond) return false;
+  const double k = h / N2;
+  const TmV d = {cn.x * k, cn.y * k, cn.z * k}, cd = tm_sub(c, d);
+  const TmV a = {fabs(c.x) + fabs(d.x), fabs(c.y) + fabs(d.y), fabs(c.z) + fabs(d.z)};
+  double rho2 = b[3] - h * k, nt2 = n2 - g * (g / N2);
+  rho2 = (rho2 > 0.0 ? rho2 : 0.0) * (1.0 + 1e-9) + 1e-9 * b[3];
+  nt2 = (nt2 > 0.0 ? nt2 : 0.0) + 1e-9 * n2;
+  const double fc = tm_dot(n, tm_sub(cd, apex));
+  return tm_pt_outside(n, apex, cd, a, 1e-9) && fc * fc > rho2 * nt2;
+}
+
+// Is object o outside the half-space n . (x - apex) >= 0: its box, else one of its vertex sets, else its ball.
+RT_TM_HD bool tm_obj_outside(const RtTileMaskScene& S, int o, TmV n, TmV apex) {
+  if (tm_all_outside(n, apex, S.blo[o], S.bhi[o])) return true;
+  for (int q = S.set_begin[o]; q < S.set_begin[o + 1]; ++q) {
+    bool out = true;
+    for (int k = 0; k < 8 && out; ++k) {
+      const TmV c = tm_ld(S.sets[q][k]);
+      out = tm_pt_outside(n, apex, c, tm_abs(c), 1e-12);
+    }
+    if (out) return true;
+  }
+  return ((S.balled >> o) & 1u) && tm_ball_outside(n, apex, S.ball[o]);
+}
+
+// The same for the part of the object inside the half-space cn . (x - cp) >= 0.
+RT_TM_HD bool tm_obj_outside_clipped(const RtTileMaskScene& S, int o, TmV n, TmV apex, TmV cn, TmV cp) {
+  TmV c[8];
+  tm_box_corners(S.blo[o], S.bhi[o], c);
+  if (tm_clip_outside(c, n, apex, cn, cp)) return true;
+  for (int q = S.set_begin[o]; q < S.set_begin[o + 1]; ++q) {
+    for (int k = 0; k < 8; ++k) c[k] = tm_ld(S.sets[q][k]);
+    if (tm_clip_outside(c, n, apex, cn, cp)) return true;
+  }
+  return ((S.balled >> o) & 1u) && tm_ball_outside_clipped(n, apex, S.ball[o], cn, cp);
+}
+
 // The four side planes (inward normals) of the cone / pyramid from `apex` through the points
 // apex + v[0..3] (in order around the rim).  False: the four are not in convex position.
 RT_TM_HD bool tm_side_planes(const TmV v[4], TmV n[4]) {
@@ -135,12 +288,12 @@ RT_TM_HD bool tm_side_planes(const TmV v[4], TmV n[4]) {
   return true;
 }
 
-// Clears from *word the boxed objects whose box lies outside one of the four side planes.
+// Clears from *word the boxed objects that lie outside one of the four side planes.
 RT_TM_HD void tm_cull_sides(const RtTileMaskScene& S, const TmV n[4], TmV apex, uint32_t* word) {
   for (int o = 0; o < S.n_objects; ++o) {
     if (!((S.boxed >> o) & 1u) || !((*word >> o) & 1u)) continue;
     for (int i = 0; i < 4; ++i)
-      if (tm_all_outside(n[i], apex, S.blo[o], S.bhi[o])) { *word &= ~(1u << o); break; }
+      if (tm_obj_outside(S, o, n[i], apex)) { *word &= ~(1u << o); break; }
   }
 }
 
@@ -214,12 +367,13 @@ RT_TM_HD void tilemask_eval(const RtTileMaskScene& S, int x0, int x1, int y0, in
         if (!((S.boxed >> o) & 1u)) continue;
         const double* lo = S.blo[o];
         const double* hi = S.bhi[o];
-        bool cull = tm_all_outside(up, Q[0], lo, hi) || tm_all_outside(down, L, lo, hi);
+        bool cull = tm_obj_outside(S, o, up, Q[0]) || tm_obj_outside(S, o, down, L);
         for (int a = 0; a < 3 && !cull; ++a) {
           const double tol = 1e-9 * (1.0 + fabs(alo[a]) + fabs(ahi[a]));
           cull = lo[a] > ahi[a] + tol || hi[a] < alo[a] - tol;
         }
-        for (int i = 0; i < 4 && !cull && sides; ++i) cull = tm_all_outside(m[i], L, lo, hi);
+        // the side planes see only what lies on the floor's side of the plane through L
+        for (int i = 0; i < 4 && !cull && sides; ++i) cull = tm_obj_outside_clipped(S, o, m[i], L, down, L);
         if (cull) w &= ~(1u << o);
       }
       out[1 + l] = w;
@@ -236,7 +390,7 @@ RT_TM_HD void tilemask_eval(const RtTileMaskScene& S, int x0, int x1, int y0, in
       if (tm_side_planes(v, m)) tm_cull_sides(S, m, Cm, &w);
       const TmV cs = sC > 0.0 ? pn : TmV{-pn.x, -pn.y, -pn.z};              // towards the camera's side
       for (int o = 0; o < S.n_objects; ++o)
-        if (((S.boxed >> o) & 1u) && tm_all_outside(cs, Q[0], S.blo[o], S.bhi[o])) w &= ~(1u << o);
+        if (((S.boxed >> o) & 1u) && ((w >> o) & 1u) && tm_obj_outside(S, o, cs, Q[0])) w &= ~(1u << o);
       out[5] = w;
     }
   }

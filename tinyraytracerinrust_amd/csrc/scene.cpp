@@ -524,6 +524,41 @@ static void const_filters(FlatScene& f, const RtObject& ob) {
 // box, so t <= 8e6 and the error is < 1e-8 (|M_i| + |T_i|); the margin is 1e-6 (1 + |M_i| + |T_i|)
 // plus 1e-6 of the box coordinates, and the slab arithmetic itself is the world box test's
 // (cull_ray / box_may_hit).
+// Leaf r's box in its own frame, inflated by the margins above, when r is such a leaf R of the object
+// (the tile masks take the same leaves, k_masks.hip tilemask_scene).  False: not required, a singular
+// or non-finite transform, or a box beyond the culling range.
+bool required_leaf_box(const FlatScene& f, const RtObject& ob, int32_t r, double lo[3], double hi[3], double* det_out) {
+  const RtLeaf& R = f.leaves[r];
+  if (R.kind != RT_N_SPHERE && R.kind != RT_N_CUBE) return false;
+  bool all = true;
+  for (int32_t x = ob.leaf_begin; x < ob.leaf_begin + ob.leaf_count && all; ++x) {
+    if (x == r) continue;
+    const RtLeaf& X = f.leaves[x];
+    bool req = false;
+    for (int k = 0; k < X.n_lit && !req; ++k) req = X.lit[k] == 2 * r + 1;
+    all = req;                       // n_lit < 0 (a disjunctive filter): never required
+  }
+  if (!all) return false;
+  for (int i = 0; i < 3; ++i) {
+    lo[i] = R.kind == RT_N_SPHERE ? R.c[i] - R.r_eps : R.lo[i];
+    hi[i] = R.kind == RT_N_SPHERE ? R.c[i] + R.r_eps : R.hi[i];
+  }
+  const double* M = R.inv;
+  const double det = M[0] * (M[5] * M[10] - M[6] * M[9]) - M[1] * (M[4] * M[10] - M[6] * M[8]) +
+                     M[2] * (M[4] * M[9] - M[5] * M[8]);
+  if (!std::isfinite(det) || !(fabs(det) > 1e-300)) return false;
+  bool ok = true;
+  for (int i = 0; i < 3 && ok; ++i) {
+    const double mi = fabs(M[4 * i]) + fabs(M[4 * i + 1]) + fabs(M[4 * i + 2]), ti = fabs(M[4 * i + 3]) + fabs(R.inv_o[i]);
+    const double m = 1e-6 * (1.0 + mi + ti) + 1e-6 * (fabs(lo[i]) + fabs(hi[i]));
+    lo[i] -= m;
+    hi[i] += m;
+    ok = std::isfinite(lo[i]) && std::isfinite(hi[i]) && fabs(lo[i]) <= RT_CULL_COORD_MAX && fabs(hi[i]) <= RT_CULL_COORD_MAX;
+  }
+  *det_out = det;
+  return ok;
+}
+
 static void obb(FlatScene& f, RtObject* ob) {
   ob->obb_leaf = -1;
   if (ob->cull != RT_CULL_BOX || diag_env("RT_NO_OBB")) return;
@@ -531,37 +566,10 @@ static void obb(FlatScene& f, RtObject* ob) {
   for (int i = 0; i < 3; ++i) wvol *= ob->bhi[i] - ob->blo[i];
   double best = 0.5 * wvol;
   for (int32_t r = ob->leaf_begin; r < ob->leaf_begin + ob->leaf_count; ++r) {
-    const RtLeaf& R = f.leaves[r];
-    if (R.kind != RT_N_SPHERE && R.kind != RT_N_CUBE) continue;
-    bool all = true;
-    for (int32_t x = ob->leaf_begin; x < ob->leaf_begin + ob->leaf_count && all; ++x) {
-      if (x == r) continue;
-      const RtLeaf& X = f.leaves[x];
-      bool req = false;
-      for (int k = 0; k < X.n_lit && !req; ++k) req = X.lit[k] == 2 * r + 1;
-      all = req;                       // n_lit < 0 (a disjunctive filter): never required
-    }
-    if (!all) continue;
-    double lo[3], hi[3];
-    for (int i = 0; i < 3; ++i) {
-      lo[i] = R.kind == RT_N_SPHERE ? R.c[i] - R.r_eps : R.lo[i];
-      hi[i] = R.kind == RT_N_SPHERE ? R.c[i] + R.r_eps : R.hi[i];
-    }
-    const double* M = R.inv;
-    const double det = M[0] * (M[5] * M[10] - M[6] * M[9]) - M[1] * (M[4] * M[10] - M[6] * M[8]) +
-                       M[2] * (M[4] * M[9] - M[5] * M[8]);
-    if (!std::isfinite(det) || !(fabs(det) > 1e-300)) continue;
-    bool ok = true;
+    double lo[3], hi[3], det;
+    if (!required_leaf_box(f, *ob, r, lo, hi, &det)) continue;
     double vol = 1.0;
-    for (int i = 0; i < 3 && ok; ++i) {
-      const double mi = fabs(M[4 * i]) + fabs(M[4 * i + 1]) + fabs(M[4 * i + 2]), ti = fabs(M[4 * i + 3]) + fabs(R.inv_o[i]);
-      const double m = 1e-6 * (1.0 + mi + ti) + 1e-6 * (fabs(lo[i]) + fabs(hi[i]));
-      lo[i] -= m;
-      hi[i] += m;
-      ok = std::isfinite(lo[i]) && std::isfinite(hi[i]) && fabs(lo[i]) <= RT_CULL_COORD_MAX && fabs(hi[i]) <= RT_CULL_COORD_MAX;
-      vol *= hi[i] - lo[i];
-    }
-    if (!ok) continue;
+    for (int i = 0; i < 3; ++i) vol *= hi[i] - lo[i];
     vol /= fabs(det);                  // world volume of the local box
     if (vol < best) {
       best = vol;
@@ -732,6 +740,7 @@ std::string describe_flat(const FlatScene& f) {
               L.plane_axis);
     }
   }
+  s += describe_tile_bounds(f);
   return s;
 }
 

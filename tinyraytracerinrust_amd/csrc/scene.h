@@ -90,6 +90,10 @@ struct rt_scene {
 namespace rt {
 int flatten(const rt_scene& s, FlatScene* out);
 std::string describe_flat(const FlatScene& f);   // rt_scene_describe's text
+std::string describe_tile_bounds(const FlatScene& f);   // k_masks.hip: the tile masks' vertex sets and balls, as text
+// Leaf r of `ob` bounds every accepted hit of the object (scene.cpp "oriented object boxes"): its
+// inflated box in the leaf's own frame and the determinant of the leaf's inverse transform.
+bool required_leaf_box(const FlatScene& f, const RtObject& ob, int32_t r, double lo[3], double hi[3], double* det);
 // A diagnostic switch from the environment: only in a diagnostic build (make diag DIAG=-DRT_DIAG_ENV),
 // false in the product (rt_ctx.hip).
 bool diag_env(const char* name);

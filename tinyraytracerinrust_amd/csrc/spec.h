@@ -82,6 +82,7 @@ std::string spec_program_text(const SpecProgram& p, const SpecKernel& k);   // p
 SpecBound spec_bound(const SpecProgram& p, int kind);
 bool same_structure_flat(const FlatScene& a, const FlatScene& b);   // a scene family's structure test
 int tilemask_plane(const FlatScene& f);        // k_masks.hip: the mask plane's object index, -1: none
+bool tilemask_sky_ok(const FlatScene& f);      // k_masks.hip: a tile whose prim word is 0 is sky (SKY_OK)
 uint64_t fnv1a(const std::string& s);
 
 // ---- the compiler (spec_compile.cpp) ---------------------------------------------------------------

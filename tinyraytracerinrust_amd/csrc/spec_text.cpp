@@ -162,6 +162,8 @@ std::string spec_source(const FlatScene& f, const SpecFamily* fam) {
   // (a family program takes no masks: its members' planes and boxes differ)
   snprintf(buf, sizeof buf, "constexpr int MASK_PLANE = %d;\n", fam ? -1 : tilemask_plane(f));
   s += buf;
+  // sky tiles (rt_device.h rows_entry): every object is boxed or the mask plane, so prim words can be 0
+  s += std::string("constexpr bool SKY_OK = ") + (!fam && tilemask_sky_ok(f) ? "true" : "false") + ";\n";
   emit_table(s, "RtObject", "OBJECTS", f.objects, fam ? &fam->v_obj : nullptr);
   emit_table(s, "RtTrav", "TRAV", f.trav, fam ? &fam->v_trav : nullptr);
   emit_table(s, "RtTrav", "STRAV", f.strav, fam ? &fam->v_strav : nullptr);

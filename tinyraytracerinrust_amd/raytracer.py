@@ -459,6 +459,11 @@ class Renderer:
         (the default), or the tile order and the tile-indexed mask table themselves (same pixels)."""
         check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_TILE_RECORDS, 1 if on else 0))
 
+    def set_sky_fill(self, on: bool) -> None:
+        """rt_ctx_set_option(RT_OPT_SKY_FILL): waves of sky tiles (an empty ``prim`` word in the dispatch record)
+        store BLACK and return (default on); off, the records mark no tile as sky.  Same pixels."""
+        check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_SKY_FILL, 1 if on else 0))
+
     def tile_masks(self, y_first: int = 0, band_rows: Optional[int] = None, band_pitch: Optional[int] = None,
                    n_bands: int = 1) -> np.ndarray:
         """rt_ctx_tile_masks: the uploaded scene's mask table of a band launch (default: the whole frame)

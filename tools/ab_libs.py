@@ -4,7 +4,8 @@ the specialised kernels loaded (RT_OPT_SPECIALIZE 1, rt_ctx_spec_wait) unless --
 ms per frame (one event pair around --frames launches) per library, median over --rounds.
 usage: python tools/ab_libs.py LIB [LIB ...] [--config sphere1080d0|globes1080d5|globes4k|spin1080|fractal1080] [--generic]
        [--masks=-1,1,0]   per library: RT_OPT_TILE_MASKS (-1: leave it, for libraries without the option)
-       [--records=-1,1,0] per library: RT_OPT_TILE_RECORDS (-1: leave it)"""
+       [--records=-1,1,0] per library: RT_OPT_TILE_RECORDS (-1: leave it)
+       [--sky=-1,1,0]     per library: RT_OPT_SKY_FILL (-1: leave it)"""
 import argparse
 import ctypes
 import os
@@ -32,6 +33,7 @@ def main():
                                                    "(a library path may repeat); default 1 (0 with --generic)")
     ap.add_argument("--masks", default="", help="per library (in order): RT_OPT_TILE_MASKS, -1 = leave the default")
     ap.add_argument("--records", default="", help="per library (in order): RT_OPT_TILE_RECORDS, -1 = leave the default")
+    ap.add_argument("--sky", default="", help="per library (in order): RT_OPT_SKY_FILL, -1 = leave the default")
     a = ap.parse_args()
     import torch
     scene, W, H, depth = CONFIGS[a.config]
@@ -40,7 +42,8 @@ def main():
     levels = [int(v) for v in a.levels.split(",")] if a.levels else [0 if a.generic else 1] * len(a.libs)
     masks = [int(v) for v in a.masks.split(",")] if a.masks else [-1] * len(a.libs)
     records = [int(v) for v in a.records.split(",")] if a.records else [-1] * len(a.libs)
-    for path, level, mask, rec in zip(a.libs, levels, masks, records):
+    sky = [int(v) for v in a.sky.split(",")] if a.sky else [-1] * len(a.libs)
+    for path, level, mask, rec, sk in zip(a.libs, levels, masks, records, sky):
         L = ctypes.CDLL(os.path.abspath(path), mode=os.RTLD_LOCAL)
         L.rt_ctx_spec_wait.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         sc, cx = ctypes.c_void_p(), ctypes.c_void_p()
@@ -51,6 +54,8 @@ def main():
             assert L.rt_ctx_set_option(cx, 8, mask) == 0               # RT_OPT_TILE_MASKS
         if rec >= 0:
             assert L.rt_ctx_set_option(cx, 10, rec) == 0              # RT_OPT_TILE_RECORDS
+        if sk >= 0:
+            assert L.rt_ctx_set_option(cx, 11, sk) == 0               # RT_OPT_SKY_FILL
         assert L.rt_ctx_upload(cx, sc) == 0
         assert L.rt_ctx_spec_wait(cx, -1) == 0
         assert L.rt_ctx_set_option(cx, 1, 0) == 0                  # RT_OPT_TIMING off, as bench.py
@@ -91,10 +96,10 @@ def main():
         if not a.no_check and not torch.equal(outs[i], outs[0]):
             raise SystemExit(f"{a.libs[i]}: frame differs from {a.libs[0]}'s")
     print(f"{a.config} ({'generic' if a.generic else 'specialised'}), {n} frames per measurement, ms per frame, median of {a.rounds}:")
-    for path, level, mask, rec, v in zip(a.libs, levels, masks, records, res):
+    for path, level, mask, rec, sk, v in zip(a.libs, levels, masks, records, sky, res):
         w = sorted(v)
         print(f"  {w[len(w) // 2]:.4f}  ({' '.join(f'{x:.4f}' for x in v)})  {path} (RT_OPT_SPECIALIZE {level}"
-              f"{'' if mask < 0 else f', RT_OPT_TILE_MASKS {mask}'}{'' if rec < 0 else f', RT_OPT_TILE_RECORDS {rec}'})", flush=True)
+              f"{'' if mask < 0 else f', RT_OPT_TILE_MASKS {mask}'}{'' if rec < 0 else f', RT_OPT_TILE_RECORDS {rec}'}{'' if sk < 0 else f', RT_OPT_SKY_FILL {sk}'})", flush=True)
 
 
 if __name__ == "__main__":
