@@ -129,7 +129,7 @@ int rt_scene_set_max_depth(rt_scene* scene, int32_t max_depth);                 
  * stereoscopic on a scene less than 2 pixels wide.
  * Every get_pixel path follows the kind: rt_render_rows / _f64 / _row_bands / _row_bands_rgb8,
  * rt_render_points_f64, rt_trace_pixel_f64.  rt_render_ortho does not use the camera.  Out of scope for
- * two-eye scenes (RT_ERR_UNSUPPORTED): rt_antialias, rt_record_rays, rt_ctx_tile_masks, rt_scene_tile_masks. */
+ * two-eye scenes (RT_ERR_UNSUPPORTED): rt_antialias, rt_antialias_row_bands, rt_record_rays, rt_ctx_tile_masks, rt_scene_tile_masks. */
 typedef enum rt_camera_kind { RT_CAMERA_PERSPECTIVE = 0, RT_CAMERA_STEREOSCOPIC = 1, RT_CAMERA_ANAGLYPH = 2 } rt_camera_kind;
 int rt_scene_set_camera_kind(rt_scene* scene, int32_t kind, double eye_distance);
 int rt_scene_get_camera_kind(const rt_scene* scene, int32_t* kind, double* eye_distance);
@@ -257,6 +257,38 @@ int rt_render_ortho(rt_ctx* ctx, int32_t axis1, int32_t axis2, double dir1, doub
 int rt_antialias(rt_ctx* ctx, const uint8_t* src_rgba8, size_t src_stride, double threshold, int32_t level,
                  int32_t max_depth, uint8_t* dst_rgba8, size_t dst_stride, double* dst_f64, size_t f64_stride,
                  uint64_t* rays_traced, void* stream);
+/* rt_antialias for the rows of a band layout (y_first, band_rows, band_pitch, n_bands as rt_render_row_bands:
+ * band b covers frame rows [y_first + b*band_pitch, ... + band_rows), rows >= H skipped; band_rows == 0 or
+ * n_bands == 0: RT_OK, nothing written, *rays_traced = 0; band_pitch < band_rows with n_bands > 1, or
+ * y_first >= H: RT_ERR_INVALID) -- AntiAliaser::anti_alias_line_vec (antialiaser.rs:53-71) for every owned
+ * line y, the unit the reference's worker and GUI work in (debug_window.rs:298-318).  src_rgba8 is still the
+ * WHOLE quantised frame (row y + 1 is read across a band's lower edge; a pixel needs nothing else of its
+ * neighbours, the memo being cleared per pixel, :91), the output is PACKED as rt_render_row_bands packs it:
+ * band b row j at output row b*band_rows + j, so dst_rgba8 / dst_f64 need n_bands*band_rows rows, and skipped
+ * rows are not written.  Every written row equals that frame row of rt_antialias' output bit for bit (RGBA8
+ * and f64), the copied last column and -- if a band owns it -- the passed-through frame row H - 1 included;
+ * *rays_traced counts the owned rows' sub-pixel rays, so over any partition of the frame into bands the counts
+ * sum to rt_antialias'.  After a multi-GPU render's all-gather every rank holds the whole quantised frame, so
+ * each anti-aliases its own bands with no halo exchange and rt_assemble_row_bands places the gathered slots
+ * (RGBA8, or f64 rows with row_bytes = 32 * width).  Everything else as rt_antialias: device or host pointers
+ * (a host output is staged for the owned rows only, a host source whole), level <= 4, the call returns when
+ * its rows are done (one host synchronisation for the edge count and one per level, whatever the row count),
+ * two-eye scenes RT_ERR_UNSUPPORTED. */
+int rt_antialias_row_bands(rt_ctx* ctx, const uint8_t* src_rgba8, size_t src_stride, double threshold, int32_t level,
+                           int32_t max_depth, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch,
+                           uint32_t n_bands, uint8_t* dst_rgba8, size_t dst_stride, double* dst_f64,
+                           size_t f64_stride, uint64_t* rays_traced, void* stream);
+/* The GUI's "show edges" overlay (check_anti_aliasing_threshold, debug_window.rs:116-139, through
+ * AntiAliaser::mark_edge_pixels, antialiaser.rs:173-191) for a whole quantised frame of the uploaded scene's
+ * size: pixel (x, y) with x < W - 1 and y < H - 1 whose mean |dRGBA| to its lower, right or lower-right
+ * neighbour exceeds threshold gets Color(0.6, 1.0, 1.0, 0.5) quantised as every frame is (153, 255, 255, 127),
+ * every other pixel Color::EMPTY (0, 0, 0, 0).  This is rt_antialias' edge predicate WITHOUT its level term: the
+ * marking does not depend on the level.  *n_edges (may be NULL) = the number of marked pixels; reading it
+ * synchronises the host with `stream`, as host pointers do (device or host pointers; overlay rows 4-byte
+ * aligned).  The GUI's antialiased_lines filter (:128) is host state and stays with the host.  NaN
+ * threshold: RT_ERR_INVALID.  The predicate reads no camera, so two-eye scenes are served too. */
+int rt_antialias_edges(rt_ctx* ctx, const uint8_t* src_rgba8, size_t src_stride, double threshold,
+                       uint8_t* overlay_rgba8, size_t overlay_stride, uint32_t* n_edges, void* stream);
 /* Milliseconds of the last render launch on this context (HIP events recorded on the launch's
  * stream around the kernel; RT_OPT_TIMING 0 turns them off and this call then fails). */
 int rt_ctx_last_kernel_ms(rt_ctx* ctx, float* ms);

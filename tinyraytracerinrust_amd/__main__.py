@@ -3,6 +3,7 @@
     python -m tinyraytracerinrust_amd render SCENE [--size WxH] [--time T | --frame F]
                                           [--depth D] [--gpus N] [-o out.png]
                                           [--camera {perspective,stereoscopic,anaglyph} --eye-distance D]
+                                          [--antialias [--aa-threshold T] [--aa-level L]]
 
 Replaces the reference's entry point and its GUI load path for this purpose: ``main()`` only
 starts the GTK application (src/main.rs:7-9), which builds a RayTracer per frame with
@@ -47,10 +48,23 @@ def _parse(argv):
                    help="the scene's Camera (camera.rs): stereoscopic = two eyes side by side, anaglyph = red/cyan")
     r.add_argument("--eye-distance", type=float, default=None,
                    help="distance between the two eyes, scene units (required for stereoscopic / anaglyph)")
+    r.add_argument("--antialias", action="store_true",
+                   help="run the adaptive anti-aliasing pass over the rendered frame (antialiaser.rs; the GUI's "
+                        "\"Anti-alias\" button); with --gpus N every rank anti-aliases the bands it rendered")
+    r.add_argument("--aa-threshold", type=float, default=0.01,
+                   help="mean |dRGBA| above which a cell subdivides (the GUI's ANTIALIAS_THRESHOLD, debug_window.rs:26)")
+    r.add_argument("--aa-level", type=int, default=3,
+                   help="subdivision levels, 0..4 (the GUI's ANTIALIAS_LEVEL, debug_window.rs:27)")
     r.add_argument("-o", "--output", default="out.png")
     a = ap.parse_args(argv)
     if a.camera != "perspective" and a.eye_distance is None:
         ap.error(f"--camera {a.camera} needs --eye-distance (the reference constructs neither camera: no default)")
+    if a.antialias and a.camera != "perspective":
+        ap.error(f"--antialias is not built for --camera {a.camera} (the pass traces perspective sub-pixels)")
+    if not 0 <= a.aa_level <= 4:
+        ap.error("--aa-level must be in 0..4")
+    if a.aa_threshold != a.aa_threshold:
+        ap.error("--aa-threshold must be a number")
     try:
         w, h = a.size.lower().split("x")
         a.width, a.height = int(w), int(h)
@@ -133,6 +147,20 @@ def render(a) -> dict:
         frame = D.assemble(gath, H, world, a.layout, band)
         torch.cuda.synchronize(dev)
         times["gather_assemble_ms"] = (time.perf_counter() - t0) * 1e3
+    aa_rays = None
+    if a.antialias:
+        # the pass reads the QUANTISED frame every rank now holds, so each rank anti-aliases the bands it
+        # rendered (no halo exchange) and a second gather of the same shape assembles the result
+        t0 = time.perf_counter()
+        if world == 1:
+            frame, aa_rays = r.antialias(frame, a.aa_threshold, a.aa_level, max_depth=a.depth)
+        else:
+            def antialias_bands(src, y_first, band_rows, pitch, n_bands, out_slot):
+                return r.antialias_row_bands(src, y_first, band_rows, pitch, n_bands, a.aa_threshold, a.aa_level,
+                                             max_depth=a.depth, out=out_slot)[1]
+            frame, aa_rays = D.antialias_frame_distributed(antialias_bands, frame.contiguous(), H, W, dev, a.layout, band)
+        torch.cuda.synchronize(dev)
+        times["antialias_ms"] = (time.perf_counter() - t0) * 1e3
     if rank == 0:
         t0 = time.perf_counter()
         host = frame.cpu().numpy()
@@ -143,7 +171,7 @@ def render(a) -> dict:
     if world > 1:
         dist.destroy_process_group()
     return {"output": a.output, "width": W, "height": H, "time": a.t, "gpus": world,
-            **{k: round(v, 3) for k, v in times.items()}}
+            **{k: round(v, 3) for k, v in times.items()}, **({"aa_rays": aa_rays} if a.antialias else {})}
 
 
 def main(argv=None) -> int:

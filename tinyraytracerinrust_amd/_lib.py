@@ -129,6 +129,11 @@ SIGNATURES = {
                              ctypes.c_uint32, ctypes.c_uint32, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P]),
     "rt_antialias": (_I, [_P, _P, ctypes.c_size_t, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _P,
                           ctypes.c_size_t, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), _P]),
+    "rt_antialias_row_bands": (_I, [_P, _P, ctypes.c_size_t, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
+                                    _U32, _U32, _U32, _U32, _P, ctypes.c_size_t, _P, ctypes.c_size_t,
+                                    ctypes.POINTER(ctypes.c_uint64), _P]),
+    "rt_antialias_edges": (_I, [_P, _P, ctypes.c_size_t, ctypes.c_double, _P, ctypes.c_size_t,
+                                ctypes.POINTER(_U32), _P]),
     "rt_ctx_last_kernel_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
     "rt_ctx_synchronize": (_I, [_P]),
     "rt_ctx_set_option": (_I, [_P, ctypes.c_int32, ctypes.c_int32]),

@@ -1,7 +1,7 @@
 // k_views.hip -- the kernels around the row loop, behind the same C ABI (get_pixel at any point: k_points.hip):
 // the ray-debugger recording
-// (rt_record_rays; ray_debugger.rs:92-137), the adaptive anti-aliasing pass (rt_antialias;
-// antialiaser.rs:87-191), the orthogonal preview views (rt_render_ortho; debug_window.rs:166-227) and
+// (rt_record_rays; ray_debugger.rs:92-137), the adaptive anti-aliasing pass (rt_antialias, rt_antialias_row_bands;
+// antialiaser.rs:87-191) and its edge overlay (rt_antialias_edges; :173-191), the orthogonal preview views (rt_render_ortho; debug_window.rs:166-227) and
 // the multi-GPU frame assembly (rt_assemble_row_bands*; debug_window.rs:147-163).
 #include <stdio.h>
 #include <stdlib.h>
@@ -70,23 +70,37 @@ struct AaGrid {             // per edge pixel: size*size colours + have bits
 #define RT_AA_MAX_LEVEL 4
 #define RT_AA_HAVE_WORDS 5  // (2^4 + 1)^2 = 289 bits
 
+// The rows a call owns: rt_render_row_bands' geometry (rt_device.h band_row).  The source is always the whole
+// frame; the OUTPUT holds the owned rows packed, n_rows of them (the host has dropped the rows >= H, which can
+// only be the layout's last).  The whole frame is the one band (0, H, H, H): a wave-uniform branch, no division.
+struct AaBands { int y_first, band_rows, band_pitch, n_rows; };
+
+__device__ __forceinline__ int aa_packed_row(const AaBands& B, int y) {   // band_row's inverse, for an owned row
+  const int d = y - B.y_first;
+  if (B.band_rows >= B.n_rows) return d;
+  return (d / B.band_pitch) * B.band_rows + d % B.band_pitch;
+}
+
+// 16x16 tiles over (W, packed rows): tiles straddle bands when band_rows is no multiple of 8; the edge list
+// keeps FRAME coordinates, so only this kernel's and aa_resolve's stores know about packing.
 __global__ __launch_bounds__(256) void aa_classify_kernel(const uint8_t* __restrict__ src, size_t stride, int W, int H,
-                                                          double th, int level, uint8_t* u8, size_t u8_stride,
+                                                          AaBands B, double th, int level, uint8_t* u8, size_t u8_stride,
                                                           double* f64, size_t f64_stride, uint32_t* __restrict__ edges,
                                                           uint32_t* __restrict__ n_edges) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int tiles_x = (W + 15) >> 4;
   const int x = ((blockIdx.x % tiles_x) << 4) + ((wave & 1) << 3) + (lane & 7);
-  const int y = ((blockIdx.x / tiles_x) << 4) + ((wave >> 1) << 3) + (lane >> 3);
+  const int r = ((blockIdx.x / tiles_x) << 4) + ((wave >> 1) << 3) + (lane >> 3);
+  const int y = band_row(r, B.y_first, B.band_rows, B.band_pitch, B.n_rows);
   bool edge = false;
-  if (x < W && y < H) {
+  if (x < W && r < B.n_rows) {               // every packed row below n_rows is a frame row (the host drops the others)
     if (x == W - 1 || y == H - 1) {          // last column copied (:67-68); last row never touched (debug_window.rs:298)
-      aa_put(aa_src(src, stride, x, y), x, y, u8, u8_stride, f64, f64_stride);
+      aa_put(aa_src(src, stride, x, y), x, r, u8, u8_stride, f64, f64_stride);
     } else {
       const AaCol c1 = aa_src(src, stride, x, y), c2 = aa_src(src, stride, x + 1, y);
       const AaCol c3 = aa_src(src, stride, x, y + 1), c4 = aa_src(src, stride, x + 1, y + 1);
       edge = level > 0 && (aa_diff(c1, c2, th) || aa_diff(c1, c3, th) || aa_diff(c1, c4, th));
-      if (!edge) aa_put(aa_avg(c1, c2, c3, c4), x, y, u8, u8_stride, f64, f64_stride);
+      if (!edge) aa_put(aa_avg(c1, c2, c3, c4), x, r, u8, u8_stride, f64, f64_stride);
     }
   }
   const uint64_t m = __ballot(edge);                                   // wave-aggregated compaction
@@ -95,6 +109,30 @@ __global__ __launch_bounds__(256) void aa_classify_kernel(const uint8_t* __restr
   if (lane == __ffsll((long long)m) - 1) base = atomicAdd(n_edges, (uint32_t)__popcll(m));
   base = __shfl(base, __ffsll((long long)m) - 1);
   if (edge) edges[base + __popcll(m & ((1ull << lane) - 1))] = ((uint32_t)y << 16) | (uint32_t)x;
+}
+
+// AntiAliaser::mark_edge_pixels (:173-191) as check_anti_aliasing_threshold paints it (debug_window.rs:116-139):
+// the classify kernel's corner predicate without its level term, over the whole frame.  One thread per pixel
+// writes `mark` or Color::EMPTY; one ballot + one atomic per wave counts the marks.
+__global__ __launch_bounds__(256) void aa_edges_kernel(const uint8_t* __restrict__ src, size_t stride, int W, int H,
+                                                       double th, uint8_t* __restrict__ out, size_t out_stride,
+                                                       uint32_t* __restrict__ n_marked) {
+  const uint32_t mark = to_u8(0.6) | (to_u8(1.0) << 8) | (to_u8(1.0) << 16) | (to_u8(0.5) << 24);   // debug_window.rs:130
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int tiles_x = (W + 15) >> 4;
+  const int x = ((blockIdx.x % tiles_x) << 4) + ((wave & 1) << 3) + (lane & 7);
+  const int y = ((blockIdx.x / tiles_x) << 4) + ((wave >> 1) << 3) + (lane >> 3);
+  bool edge = false;
+  if (x < W && y < H) {
+    if (x < W - 1 && y < H - 1) {
+      const AaCol c1 = aa_src(src, stride, x, y);
+      edge = aa_diff(c1, aa_src(src, stride, x, y + 1), th) || aa_diff(c1, aa_src(src, stride, x + 1, y), th) ||
+             aa_diff(c1, aa_src(src, stride, x + 1, y + 1), th);
+    }
+    ((uint32_t*)(out + (size_t)y * out_stride))[x] = edge ? mark : 0u;
+  }
+  const uint64_t m = __ballot(edge);
+  if (m != 0 && lane == __ffsll((long long)m) - 1) atomicAdd(n_marked, (uint32_t)__popcll(m));
 }
 
 __device__ __forceinline__ bool aa_has(const uint64_t* h, int i) { return (h[i >> 6] >> (i & 63)) & 1u; }
@@ -221,14 +259,14 @@ __device__ AaCol aa_cell(const AaCol* col, int sz, int x1, int y1, int x2, int y
 }
 
 __global__ __launch_bounds__(256) void aa_resolve_kernel(AaGrid G, const uint32_t* __restrict__ edges, uint32_t n,
-                                                         int level, double th, uint8_t* u8, size_t u8_stride,
-                                                         double* f64, size_t f64_stride) {
+                                                         int level, double th, AaBands B, uint8_t* u8,
+                                                         size_t u8_stride, double* f64, size_t f64_stride) {
   const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
   const int sz = G.size;
   const AaCol* col = G.col + (size_t)e * sz * sz;
   const AaCol res = aa_cell<RT_AA_MAX_LEVEL>(col, sz, 0, 0, sz - 1, sz - 1, level, th);
-  aa_put(res, edges[e] & 0xffff, edges[e] >> 16, u8, u8_stride, f64, f64_stride);
+  aa_put(res, edges[e] & 0xffff, aa_packed_row(B, edges[e] >> 16), u8, u8_stride, f64, f64_stride);
 }
 
 // ====================================================================== orthogonal preview views
@@ -391,13 +429,16 @@ int rt_assemble_row_bands_rgb8(const uint8_t* gathered, size_t gathered_stride, 
   return RT_OK;
 }
 
-// antialiaser.rs:87-191 over a whole quantised frame (see the kernels above).
-int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double threshold, int32_t level,
-                 int32_t max_depth, uint8_t* dst_rgba8, size_t dst_stride, double* dst_f64, size_t f64_stride,
-                 uint64_t* rays_traced, void* stream) {
+// antialiaser.rs:87-191 over the rows of a band layout of a whole quantised frame (see the kernels above):
+// rt_antialias passes one band of more rows than any frame has, which the clamp to H below makes the layout
+// (0, H, H, 1); rt_antialias_row_bands passes its caller's.  `who` names the entry in the one error text that does.
+static int antialias_rows(rt_ctx* c, const char* who, const uint8_t* src_rgba8, size_t src_stride, double threshold,
+                          int32_t level, int32_t max_depth, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch,
+                          uint32_t n_bands, uint8_t* dst_rgba8, size_t dst_stride, double* dst_f64,
+                          size_t f64_stride, uint64_t* rays_traced, void* stream) {
   if (!c || !src_rgba8 || (!dst_rgba8 && !dst_f64)) return fail(RT_ERR_INVALID, "null argument");
   if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
-  if (c->views.kind) return fail(RT_ERR_UNSUPPORTED, "rt_antialias is not built for a two-eye scene (stereoscopic / anaglyph camera)");
+  if (c->views.kind) return fail(RT_ERR_UNSUPPORTED, "%s is not built for a two-eye scene (stereoscopic / anaglyph camera)", who);
   if (level < 0) level = 0;
   if (level > RT_AA_MAX_LEVEL) return fail(RT_ERR_UNSUPPORTED, "anti-aliasing level %d > %d", level, RT_AA_MAX_LEVEL);
   if (!(threshold == threshold)) return fail(RT_ERR_INVALID, "threshold is NaN");
@@ -409,6 +450,19 @@ int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double 
   if (src_stride < row4) return fail(RT_ERR_INVALID, "source stride %zu < %zu", src_stride, row4);
   if (dst_rgba8 && dst_stride < row4) return fail(RT_ERR_INVALID, "output stride %zu < %zu", dst_stride, row4);
   if (dst_f64 && f64_stride < row32) return fail(RT_ERR_INVALID, "f64 stride %zu < %zu", f64_stride, row32);
+  // the owned rows, as rt_render_row_bands reads its geometry; bands that start at or past H and the last band's
+  // rows past H are dropped here, so the kernels see n_rows packed rows that all exist
+  if (band_rows == 0 || n_bands == 0) {
+    if (rays_traced) *rays_traced = 0;
+    return RT_OK;
+  }
+  if (band_pitch < band_rows && n_bands > 1) return fail(RT_ERR_INVALID, "band pitch %u < band rows %u", band_pitch, band_rows);
+  if (y_first >= (uint32_t)H) return fail(RT_ERR_INVALID, "first row %u >= height %d", y_first, H);
+  if (n_bands > 1) n_bands = std::min(n_bands, ((uint32_t)H - 1 - y_first) / band_pitch + 1);
+  const uint32_t last_rows = std::min(band_rows, (uint32_t)H - (y_first + (n_bands - 1) * band_pitch));
+  if (n_bands == 1) band_rows = band_pitch = last_rows;
+  const uint32_t n_rows = (n_bands - 1) * band_rows + last_rows;
+  const AaBands B = {(int)y_first, (int)band_rows, (int)band_pitch, (int)n_rows};
   RT_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   // the trace passes' kernel: the scene's specialised one once it is loaded (requested here on the first call
@@ -417,13 +471,13 @@ int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double 
   const hipFunction_t sfn = spec_sample_kernel(c, SPEC_AA);
   const char* const sample_ran = c->spec.last_sample;
   c->spec.last_sample = sample_before;
-  const size_t npx = (size_t)W * H;
-  // device staging: [src u8][dst u8][dst f64][edges][counters] for host pointers
+  const size_t npx = (size_t)W * n_rows;                             // the call's pixels: outputs, edge list
+  // device staging: [src u8, the whole frame][dst u8][dst f64][edges][counters] for host pointers
   const bool d_src = is_device_ptr(src_rgba8), d_u8 = !dst_rgba8 || is_device_ptr(dst_rgba8);
   const bool d_f64 = !dst_f64 || is_device_ptr(dst_f64);
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_src = d_src ? 0 : take(npx * 4), o_u8 = d_u8 ? 0 : take(npx * 4), o_f64 = d_f64 ? 0 : take(npx * 32);
+  const size_t o_src = d_src ? 0 : take(row4 * H), o_u8 = d_u8 ? 0 : take(npx * 4), o_f64 = d_f64 ? 0 : take(npx * 32);
   const size_t o_edges = take(npx * 4), o_cnt = take(64);
   int rc = ensure_scratch(c, off);
   if (rc) return rc;
@@ -439,8 +493,8 @@ int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double 
   uint32_t* cnt = (uint32_t*)(sb + o_cnt);
   RT_HIP(hipMemsetAsync(cnt, 0, 64, st));
   if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
-  const int tiles = ((W + 15) / 16) * ((H + 15) / 16);
-  hipLaunchKernelGGL(aa_classify_kernel, dim3(tiles), dim3(256), 0, st, src, sstride, W, H, threshold, (int)level,
+  const int tiles = ((W + 15) / 16) * (((int)n_rows + 15) / 16);
+  hipLaunchKernelGGL(aa_classify_kernel, dim3(tiles), dim3(256), 0, st, src, sstride, W, H, B, threshold, (int)level,
                      u8, u8s, f64, f64s, edges, cnt);
   RT_HIP(hipGetLastError());
   uint32_t n_edges = 0;
@@ -497,7 +551,7 @@ int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double 
 #undef RT_LAUNCH_AA
     }
     if (err == RT_OK) {
-      hipLaunchKernelGGL(aa_resolve_kernel, eg, blk, 0, st, G, edges, n_edges, (int)level, threshold, u8, u8s, f64, f64s);
+      hipLaunchKernelGGL(aa_resolve_kernel, eg, blk, 0, st, G, edges, n_edges, (int)level, threshold, B, u8, u8s, f64, f64s);
       if (hipGetLastError() != hipSuccess) err = fail(RT_ERR_DEVICE, "anti-aliasing kernels failed to launch");
     }
     (void)hipFreeAsync(work, st);
@@ -506,10 +560,65 @@ int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double 
   if (c->timing) RT_HIP(hipEventRecord(c->ev1, st));
   c->timed = c->timing;
   RT_TRY(rt::mark_launch(c, st));
-  if (dst_rgba8 && !d_u8) RT_HIP(hipMemcpy2DAsync(dst_rgba8, dst_stride, u8, row4, row4, H, hipMemcpyDeviceToHost, st));
-  if (dst_f64 && !d_f64) RT_HIP(hipMemcpy2DAsync(dst_f64, f64_stride, f64, row32, row32, H, hipMemcpyDeviceToHost, st));
+  if (dst_rgba8 && !d_u8) RT_HIP(hipMemcpy2DAsync(dst_rgba8, dst_stride, u8, row4, row4, n_rows, hipMemcpyDeviceToHost, st));
+  if (dst_f64 && !d_f64) RT_HIP(hipMemcpy2DAsync(dst_f64, f64_stride, f64, row32, row32, n_rows, hipMemcpyDeviceToHost, st));
   RT_HIP(hipStreamSynchronize(st));
   if (rays_traced) *rays_traced = rays;
+  return RT_OK;
+}
+
+int rt_antialias(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double threshold, int32_t level,
+                 int32_t max_depth, uint8_t* dst_rgba8, size_t dst_stride, double* dst_f64, size_t f64_stride,
+                 uint64_t* rays_traced, void* stream) {
+  return antialias_rows(c, "rt_antialias", src_rgba8, src_stride, threshold, level, max_depth, 0, UINT32_MAX, UINT32_MAX, 1,
+                        dst_rgba8, dst_stride, dst_f64, f64_stride, rays_traced, stream);
+}
+
+int rt_antialias_row_bands(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double threshold, int32_t level,
+                           int32_t max_depth, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
+                           uint8_t* dst_rgba8, size_t dst_stride, double* dst_f64, size_t f64_stride,
+                           uint64_t* rays_traced, void* stream) {
+  return antialias_rows(c, "rt_antialias_row_bands", src_rgba8, src_stride, threshold, level, max_depth, y_first, band_rows,
+                        band_pitch, n_bands, dst_rgba8, dst_stride, dst_f64, f64_stride, rays_traced, stream);
+}
+
+// AntiAliaser::mark_edge_pixels (antialiaser.rs:173-191) into an overlay, as check_anti_aliasing_threshold
+// (debug_window.rs:116-139) builds the GUI's "show edges" layer.
+int rt_antialias_edges(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, double threshold, uint8_t* overlay_rgba8,
+                       size_t overlay_stride, uint32_t* n_edges, void* stream) {
+  if (!c || !src_rgba8 || !overlay_rgba8) return fail(RT_ERR_INVALID, "null argument");
+  if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
+  if (!(threshold == threshold)) return fail(RT_ERR_INVALID, "threshold is NaN");
+  const int W = c->dev.width, H = c->dev.height;
+  const size_t row4 = (size_t)W * 4;
+  if (src_stride < row4) return fail(RT_ERR_INVALID, "source stride %zu < %zu", src_stride, row4);
+  if (overlay_stride < row4) return fail(RT_ERR_INVALID, "overlay stride %zu < %zu", overlay_stride, row4);
+  RT_HIP(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const bool d_src = is_device_ptr(src_rgba8), d_out = is_device_ptr(overlay_rgba8);
+  if (d_out && (((uintptr_t)overlay_rgba8 | overlay_stride) & 3)) return fail(RT_ERR_INVALID, "overlay rows must be 4-byte aligned");
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+  const size_t o_src = d_src ? 0 : take(row4 * H), o_out = d_out ? 0 : take(row4 * H), o_cnt = take(64);
+  int rc = ensure_scratch(c, off);
+  if (rc) return rc;
+  uint8_t* sb = (uint8_t*)c->scratch;
+  const uint8_t* src = d_src ? src_rgba8 : sb + o_src;
+  size_t sstride = src_stride;
+  if (!d_src) { RT_HIP(hipMemcpy2DAsync(sb + o_src, row4, src_rgba8, src_stride, row4, H, hipMemcpyHostToDevice, st)); sstride = row4; }
+  uint8_t* out = d_out ? overlay_rgba8 : sb + o_out;
+  const size_t ostride = d_out ? overlay_stride : row4;
+  uint32_t* cnt = (uint32_t*)(sb + o_cnt);
+  RT_HIP(hipMemsetAsync(cnt, 0, 64, st));
+  const int tiles = ((W + 15) / 16) * ((H + 15) / 16);
+  hipLaunchKernelGGL(aa_edges_kernel, dim3(tiles), dim3(256), 0, st, src, sstride, W, H, threshold, out, ostride, cnt);
+  RT_HIP(hipGetLastError());
+  RT_TRY(rt::mark_launch(c, st));
+  if (!d_out) RT_HIP(hipMemcpy2DAsync(overlay_rgba8, overlay_stride, out, row4, row4, H, hipMemcpyDeviceToHost, st));
+  uint32_t n = 0;
+  if (n_edges) RT_HIP(hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, st));
+  if (n_edges || !d_out || !d_src) RT_HIP(hipStreamSynchronize(st));
+  if (n_edges) *n_edges = n;
   return RT_OK;
 }
 

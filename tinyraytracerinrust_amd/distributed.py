@@ -188,3 +188,27 @@ def render_frame_distributed(render_rows: Callable[[int, int, torch.Tensor], Non
     gathered = torch.empty((world * slot.shape[0], width, 4), dtype=slot.dtype, device=slot.device)
     dist.all_gather_into_tensor(gathered, slot, group=group)
     return assemble(gathered, height, world, layout, band) if assemble_frame else gathered
+
+
+def antialias_frame_distributed(antialias_bands: Callable[[torch.Tensor, int, int, int, int, torch.Tensor], int],
+                                frame: torch.Tensor, height: int, width: int, device, layout: str = "contiguous",
+                                band: int = 16, group=None) -> Tuple[torch.Tensor, int]:
+    """The adaptive anti-aliasing pass over the ranks that rendered ``frame``.
+
+    After render_frame_distributed every rank holds the whole quantised (H, W, 4) RGBA8 frame, and a pixel
+    of the pass reads only its right, lower and lower-right neighbours of THAT frame, so each rank
+    anti-aliases exactly the rows it rendered with no halo exchange: ``antialias_bands(frame, y_first,
+    band_rows, band_pitch, n_bands, out_slot)`` (Renderer.antialias_row_bands on a GPU) writes them packed
+    into this rank's slot and returns its sub-pixel ray count.  A second all-gather of the render's shape
+    and the same assembly give every rank the anti-aliased frame; the ray counts are all-reduced.
+    Returns (frame, total rays)."""
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    slot = torch.zeros((rows_per_rank(height, world, layout, band), width, 4), dtype=torch.uint8, device=device)
+    y_first, band_rows, band_pitch, n_bands = band_params(height, world, rank, layout, band)
+    rays = int(antialias_bands(frame, y_first, band_rows, band_pitch, n_bands, slot)) if n_bands and band_rows else 0
+    gathered = torch.empty((world * slot.shape[0], width, 4), dtype=slot.dtype, device=slot.device)
+    dist.all_gather_into_tensor(gathered, slot, group=group)
+    total = torch.tensor([rays], dtype=torch.int64, device=slot.device)
+    dist.all_reduce(total, op=dist.ReduceOp.SUM, group=group)
+    return assemble(gathered, height, world, layout, band), int(total.item())

@@ -272,6 +272,15 @@ class Scene:
             pass
 
 
+def _check_rows(a, dtype: str, what: str) -> None:
+    """The library reads and writes packed rows of one element type behind a row stride: refuse an array
+    (numpy or torch) of another dtype, or whose rows are not contiguous, before its address is passed."""
+    if str(a.dtype).split(".")[-1] != dtype:
+        raise ValueError(f"{what} is {a.dtype}, not {dtype}")
+    if a.shape[0] and not (a[0].flags.c_contiguous if isinstance(a, np.ndarray) else a[0].is_contiguous()):
+        raise ValueError(f"the rows of the {what} must be contiguous")
+
+
 class Renderer:
     """Owner of an ``rt_ctx*``: one device, its stream, the uploaded scene."""
 
@@ -385,6 +394,66 @@ class Renderer:
                                  ctypes.c_void_p(u8p), u8s, ctypes.c_void_p(fp), fs, ctypes.byref(rays),
                                  ctypes.c_void_p(st)))
         return res, rays.value
+
+    def antialias_row_bands(self, frame, y_first: int, band_rows: int, band_pitch: int, n_bands: int,
+                            threshold: float = 0.01, level: int = 3, max_depth: int = -1, f64: bool = False,
+                            out=None, stream=None):
+        """rt_antialias_row_bands: the anti-aliasing pass for the rows of a band layout (the geometry of
+        render_row_bands).  ``frame`` is the WHOLE (H, W, 4) quantised frame, a torch tensor on this
+        device or a numpy array, as for ``antialias``.  Returns (packed rows, sub-pixel rays traced in
+        them): band b row j at row b*band_rows + j of an (n_bands*band_rows, W, 4) array (``out``, if
+        given, needs at least that many rows); rows past the frame's height are not written."""
+        rays = ctypes.c_uint64(0)
+        rows = int(band_rows) * int(n_bands)
+        if isinstance(frame, np.ndarray):
+            src = np.ascontiguousarray(frame, dtype=np.uint8)
+            res = out if out is not None else np.zeros((rows, src.shape[1], 4), np.float64 if f64 else np.uint8)
+            sp, ss, rp, rs = src.ctypes.data, src.strides[0], res.ctypes.data, res.strides[0]
+            st = 0
+        else:
+            import torch
+            src = frame
+            res = out if out is not None else torch.zeros((rows, frame.shape[1], 4),
+                                                          dtype=torch.float64 if f64 else torch.uint8, device=frame.device)
+            sp, ss = src.data_ptr(), src.stride(0) * src.element_size()
+            rp, rs = res.data_ptr(), res.stride(0) * res.element_size()
+            st = (stream if stream is not None else torch.cuda.current_stream(frame.device)).cuda_stream
+        if tuple(src.shape) != (self.height, self.width, 4):
+            raise ValueError(f"frame {tuple(src.shape)} is not the uploaded scene's {(self.height, self.width, 4)}")
+        if res.shape[0] < rows or tuple(res.shape[1:]) != (self.width, 4):
+            raise ValueError(f"output {tuple(res.shape)} holds fewer than {rows} rows of {(self.width, 4)}")
+        _check_rows(src, "uint8", "frame")
+        _check_rows(res, "float64" if f64 else "uint8", "output")
+        if res.shape[0] == 0:                 # no band and no output row: an empty tensor has no address to pass
+            return res, 0
+        u8p, u8s, fp, fs = (None, 0, rp, rs) if f64 else (rp, rs, None, 0)
+        check(lib().rt_antialias_row_bands(self.h, ctypes.c_void_p(sp), ss, float(threshold), int(level), int(max_depth),
+                                           int(y_first), int(band_rows), int(band_pitch), int(n_bands),
+                                           ctypes.c_void_p(u8p), u8s, ctypes.c_void_p(fp), fs, ctypes.byref(rays),
+                                           ctypes.c_void_p(st)))
+        return res, rays.value
+
+    def antialias_edges(self, frame, threshold: float = 0.01):
+        """rt_antialias_edges: the GUI's "show edges" overlay of a whole quantised frame (torch device
+        tensor or numpy array, as for ``antialias``).  Returns ((H, W, 4) uint8 overlay, marked pixels)."""
+        n = ctypes.c_uint32(0)
+        if isinstance(frame, np.ndarray):
+            src = np.ascontiguousarray(frame, dtype=np.uint8)
+            res = np.empty(src.shape, np.uint8)
+            sp, ss, rp, rs = src.ctypes.data, src.strides[0], res.ctypes.data, res.strides[0]
+            st = 0
+        else:
+            import torch
+            src = frame
+            res = torch.empty(tuple(frame.shape), dtype=torch.uint8, device=frame.device)
+            sp, ss, rp, rs = src.data_ptr(), src.stride(0), res.data_ptr(), res.stride(0)
+            st = torch.cuda.current_stream(frame.device).cuda_stream
+        if tuple(src.shape) != (self.height, self.width, 4):
+            raise ValueError(f"frame {tuple(src.shape)} is not the uploaded scene's {(self.height, self.width, 4)}")
+        _check_rows(src, "uint8", "frame")
+        check(lib().rt_antialias_edges(self.h, ctypes.c_void_p(sp), ss, float(threshold), ctypes.c_void_p(rp), rs,
+                                       ctypes.byref(n), ctypes.c_void_p(st)))
+        return res, n.value
 
     def record_rays(self, x: float, y: float, max_depth: int = -1, cap: int = 1 << 17):
         """rt_record_rays: (records as a RAY_RECORD_DTYPE array in callback order, pixel colour)."""
@@ -740,8 +809,8 @@ class AntiAliaser:
 
     ``AntiAliaser(ray_tracer, threshold=None, level=None)`` takes the reference's defaults
     (0.1 and 3, antialiaser.rs:18-19); the GUI passes ANTIALIAS_THRESHOLD = 0.01 and
-    ANTIALIAS_LEVEL = 3 (debug_window.rs:26-27).  The whole frame is one GPU pass (rt_antialias);
-    ``ray_counter`` accumulates the sub-pixel rays traced like the reference's counter."""
+    ANTIALIAS_LEVEL = 3 (debug_window.rs:26-27).  The whole frame is one GPU pass (rt_antialias), a
+    line one band of one row (rt_antialias_row_bands); ``ray_counter`` accumulates the sub-pixel rays traced like the reference's counter."""
 
     def __init__(self, ray_tracer: "RayTracer", threshold: Optional[float] = None, level: Optional[int] = None):
         self.ray_tracer = ray_tracer
@@ -760,6 +829,20 @@ class AntiAliaser:
                                                        f64=f64)
         self.ray_counter += rays
         return out
+
+    def anti_alias_line_vec(self, y: int, source) -> np.ndarray:
+        """``anti_alias_line_vec(y, ..)`` (antialiaser.rs:53-71): line y of the whole quantised frame
+        ``source`` as its W colours, (W, 4) float64 -- one band of one row (rt_antialias_row_bands).
+        Adds the line's sub-pixel rays to ``ray_counter``.  The line reads row y + 1, so y must be below
+        H - 1, as the reference's worker keeps it (debug_window.rs:298)."""
+        h = source.shape[0]
+        if not 0 <= y < h - 1:
+            raise IndexError(f"line {y} outside 0..{h - 2}: the last row has no row below it and is never anti-aliased")
+        out, rays = self.ray_tracer.renderer.antialias_row_bands(source, y, 1, 1, 1, self.threshold, self.level,
+                                                                 self.ray_tracer.max_depth, f64=True)
+        self.ray_counter += rays
+        line = out[0]
+        return line if isinstance(line, np.ndarray) else line.cpu().numpy()
 
 
 def _ortho_line(rt: "RayTracer", y: int, ortho_axes: OrthoAxes) -> np.ndarray:
