@@ -247,32 +247,15 @@ void drop_rec(rt_ctx::RecSlot& s) {
   s = rt_ctx::RecSlot();
 }
 
-// Geometry of a band launch as launch_bands computes it
-int mask_geometry(int width, int height, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
-                  int* n_rows, size_t* n_tiles) {
-  if (band_rows == 0 || n_bands == 0) return fail(RT_ERR_INVALID, "no rows");
-  if (band_pitch < band_rows && n_bands > 1) return fail(RT_ERR_INVALID, "band pitch %u < band rows %u", band_pitch, band_rows);
-  if (y_first >= (uint32_t)height) return fail(RT_ERR_INVALID, "first row %u >= height %d", y_first, height);
-  const uint64_t rows = (uint64_t)band_rows * n_bands;
-  if (rows > (1u << 24)) return fail(RT_ERR_INVALID, "too many rows");
-  *n_rows = (int)rows;
-  const int tiles_x = (width + RT_TILE_W - 1) / RT_TILE_W, tile_h = 64 / RT_TILE_W;
-  *n_tiles = (size_t)tiles_x * (size_t)((rows + tile_h - 1) / tile_h);
-  return RT_OK;
-}
+}  // namespace
 
-// The slot of a geometry, filled on st if it is new since the upload
+namespace rt {
+
 int mask_slot(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t n_tiles, rt_ctx::MaskSlot** out) {
   const int32_t key[5] = {a0, a1, a2, a3, c->dev.width};
-  rt_ctx::MaskSlot* slot = nullptr;
-  for (auto& s : c->masks)
-    if (s.valid && memcmp(s.key, key, sizeof key) == 0) slot = &s;
-  if (!slot) {
-    slot = &c->masks[0];
-    for (auto& s : c->masks) {
-      if (!s.valid) { slot = &s; break; }
-      if (s.last_use < slot->last_use) slot = &s;
-    }
+  bool found;
+  rt_ctx::MaskSlot* slot = find_slot(c->masks, [&](const rt_ctx::MaskSlot& s) { return memcmp(s.key, key, sizeof key) == 0; }, &found);
+  if (!found) {
     drop_mask(*slot);
     RT_HIP(hipMalloc((void**)&slot->d_masks, n_tiles * RT_TILEMASK_WORDS * sizeof(uint32_t)));
     RT_HIP(hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming));
@@ -287,21 +270,9 @@ int mask_slot(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t 
     slot->valid = true;
   }
   slot->last_use = ++c->use_clock;
-  if (!slot->seen_ready && slot->fill_stream != st) {      // another stream's launch: after the fill
-    if (hipEventQuery(slot->ready) == hipSuccess) {
-      slot->seen_ready = true;
-    } else {
-      (void)hipGetLastError();
-      RT_HIP(hipStreamWaitEvent(st, slot->ready, 0));
-    }
-  }
   *out = slot;
-  return RT_OK;
+  return wait_ready(*slot, st);       // another stream's launch: after the fill
 }
-
-}  // namespace
-
-namespace rt {
 
 void drop_masks(rt_ctx* c) {
   for (auto& s : c->masks) drop_mask(s);
@@ -360,39 +331,25 @@ size_t put_mask_scene(const FlatScene& f, std::vector<uint8_t>& blob, bool* ok) 
   return off;
 }
 
-int launch_masks(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t n_tiles, const uint32_t** table,
-                 const void** mslot) {
-  *table = nullptr;
-  if (mslot) *mslot = nullptr;
-  if (!c->tile_masks || !c->masks_ok) return RT_OK;
+bool masks_usable(const rt_ctx* c) {
   static const bool off = diag_env("RT_NO_TILE_MASKS");
-  if (off) return RT_OK;
-  rt_ctx::MaskSlot* slot = nullptr;
-  RT_TRY(mask_slot(c, st, a0, a1, a2, a3, n_tiles, &slot));
-  *table = slot->d_masks;
-  if (mslot) *mslot = slot;
-  return RT_OK;
+  return c->masks_ok && !off;
 }
 
 // The record table of a masked launch: found by the mask fill it read and the calibration that wrote its order
 // (a table of an earlier fill -- the masks are dropped on every upload -- or of another order is never taken),
-// else gathered on st, behind the mask fill: launch_masks has put the fill, or a wait for its event, on st
+// else gathered on st, behind the mask fill: mask_slot has put the fill, or a wait for its event, on st
 // already.  Launches on other streams wait for the gather's own event.
-int launch_records(rt_ctx* c, hipStream_t st, const void* mask_slot, const int32_t* d_order, uint64_t order_id,
+int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const int32_t* d_order, uint64_t order_id,
                    uint32_t n_entries, const RtTileRec** table, const void** rslot) {
-  const rt_ctx::MaskSlot* ms = (const rt_ctx::MaskSlot*)mask_slot;
   *table = nullptr;
   if (rslot) *rslot = nullptr;
   const bool sky_fill = c->sky_fill && c->sky_ok;
-  rt_ctx::RecSlot* slot = nullptr;
-  for (auto& s : c->recs)
-    if (s.valid && s.fill_id == ms->fill_id && s.order_id == order_id && s.n_entries == n_entries && s.sky_fill == sky_fill) slot = &s;
-  if (!slot) {
-    slot = &c->recs[0];
-    for (auto& s : c->recs) {
-      if (!s.valid) { slot = &s; break; }
-      if (s.last_use < slot->last_use) slot = &s;
-    }
+  bool found;
+  rt_ctx::RecSlot* slot = find_slot(c->recs, [&](const rt_ctx::RecSlot& s) {
+    return s.fill_id == ms->fill_id && s.order_id == order_id && s.n_entries == n_entries && s.sky_fill == sky_fill;
+  }, &found);
+  if (!found) {
     drop_rec(*slot);
     // (one more record's room behind the table: the count of sky entries, for rt_ctx_kernel_info)
     RT_HIP(hipMalloc((void**)&slot->d_recs, ((size_t)n_entries + 1) * sizeof(RtTileRec)));
@@ -417,17 +374,9 @@ int launch_records(rt_ctx* c, hipStream_t st, const void* mask_slot, const int32
     slot->valid = true;
   }
   slot->last_use = ++c->use_clock;
-  if (!slot->seen_ready && slot->fill_stream != st) {      // another stream's launch: after the gather
-    if (hipEventQuery(slot->ready) == hipSuccess) {
-      slot->seen_ready = true;
-    } else {
-      (void)hipGetLastError();
-      RT_HIP(hipStreamWaitEvent(st, slot->ready, 0));
-    }
-  }
   *table = slot->d_recs;
   if (rslot) *rslot = slot;
-  return RT_OK;
+  return wait_ready(*slot, st);       // another stream's launch: after the gather
 }
 
 uint64_t record_id(const void* rslot) { return rslot ? ((const rt_ctx::RecSlot*)rslot)->rec_id : 0; }
@@ -454,9 +403,9 @@ int rt_ctx_tile_masks(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t 
   if (!c || !n_tiles_out || (cap_words > 0 && !words)) return fail(RT_ERR_INVALID, "null argument");
   if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
   if (c->views.kind) return fail(RT_ERR_UNSUPPORTED, "rt_ctx_tile_masks is not built for a two-eye scene (stereoscopic / anaglyph camera)");
-  int n_rows = 0;
-  size_t n_tiles = 0;
-  RT_TRY(mask_geometry(c->dev.width, c->dev.height, y_first, band_rows, band_pitch, n_bands, &n_rows, &n_tiles));
+  const rt::BandGeometry g = rt::band_geometry(c->dev.width, c->dev.height, y_first, band_rows, band_pitch, n_bands);
+  if (g.status != rt::BandGeometry::OK) return fail(RT_ERR_INVALID, "%s", g.error);
+  const size_t n_tiles = g.n_tiles;
   *n_tiles_out = (uint32_t)n_tiles;
   const size_t n = std::min(cap_words, n_tiles * RT_TILEMASK_WORDS);
   if (n == 0) return RT_OK;
@@ -466,7 +415,7 @@ int rt_ctx_tile_masks(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t 
   }
   RT_HIP(hipSetDevice(c->device));
   rt_ctx::MaskSlot* slot = nullptr;
-  RT_TRY(mask_slot(c, nullptr, (int)y_first, (int)band_rows, (int)band_pitch, n_rows, n_tiles, &slot));
+  RT_TRY(rt::mask_slot(c, nullptr, (int)y_first, (int)band_rows, (int)band_pitch, (int)g.n_rows, n_tiles, &slot));
   RT_HIP(hipStreamSynchronize(nullptr));
   RT_HIP(hipMemcpy(words, slot->d_masks, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return RT_OK;
@@ -479,9 +428,9 @@ int rt_scene_tile_masks(const rt_scene* s, uint32_t y_first, uint32_t band_rows,
     return fail(RT_ERR_UNSUPPORTED, "rt_scene_tile_masks is not built for a two-eye scene (stereoscopic / anaglyph camera)");
   rt::FlatScene f;
   RT_TRY(rt::flatten(*s, &f));
-  int n_rows = 0;
-  size_t n_tiles = 0;
-  RT_TRY(mask_geometry(f.width, f.height, y_first, band_rows, band_pitch, n_bands, &n_rows, &n_tiles));
+  const rt::BandGeometry g = rt::band_geometry(f.width, f.height, y_first, band_rows, band_pitch, n_bands);
+  if (g.status != rt::BandGeometry::OK) return fail(RT_ERR_INVALID, "%s", g.error);
+  const size_t n_tiles = g.n_tiles;
   RtTileMaskScene t;
   tilemask_scene(f, &t);
   info[0] = (int32_t)n_tiles;
@@ -491,7 +440,7 @@ int rt_scene_tile_masks(const rt_scene* s, uint32_t y_first, uint32_t band_rows,
   for (size_t tile = 0; tile < n_tiles && (tile + 1) * RT_TILEMASK_WORDS <= cap_words; ++tile) {
     uint32_t* w = words + tile * RT_TILEMASK_WORDS;
     int x0, x1, y0, y1;
-    if (tilemask_rect((unsigned)tile, f.width, f.height, (int)y_first, (int)band_rows, (int)band_pitch, n_rows, &x0, &x1, &y0, &y1))
+    if (tilemask_rect((unsigned)tile, f.width, f.height, (int)y_first, (int)band_rows, (int)band_pitch, (int)g.n_rows, &x0, &x1, &y0, &y1))
       tilemask_eval(t, x0, x1, y0, y1, w);
     else
       for (int k = 0; k < RT_TILEMASK_WORDS; ++k) w[k] = 0xffffffffu;

@@ -1,7 +1,9 @@
 // rt_ctx.h -- the device context behind the C ABI (include/rt_abi.h: rt_ctx_*), shared by the
 // host halves of the kernel translation units: rt_ctx.hip (create / upload / options / streams),
-// k_rows.hip (the row kernels' launches), k_stereo.hip (two-eye scenes' launches), k_wavefront.hip,
-// k_views.hip.  Host code only.
+// k_rows.hip (the row kernels' launches), k_stereo.hip (two-eye scenes' launches), k_masks.hip (tile masks and
+// dispatch records), k_wavefront.hip, k_views.hip, spec_ctx.hip.  The launches' decisions are launch_plan.h's
+// (pure host code, no HIP); this header holds what they share on the device side: the slot cache, the order
+// slots' acquisition and calibration, the end of a launch, the template dispatch.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,8 +11,10 @@
 
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "launch_plan.h"
 #include "rt_blob.h"
 #include "scene.h"
 #include "spec.h"
@@ -184,20 +188,75 @@ using rt::fail;
   } while (0)
 
 namespace rt {
+// The slot cache of the order, mask and record tables: the valid slot that `match` accepts (*found), else the
+// slot to fill -- an empty one, or the least recently used.  The caller drops and fills it: those differ.
+template <class Slot, size_t N, class Match>
+Slot* find_slot(Slot (&slots)[N], Match match, bool* found) {
+  Slot* lru = &slots[0];
+  *found = true;
+  for (auto& s : slots)
+    if (s.valid && match(s)) return &s;
+  *found = false;
+  for (auto& s : slots) {
+    if (!s.valid) return &s;
+    if (s.last_use < lru->last_use) lru = &s;
+  }
+  return lru;
+}
+// A launch on st reads a table (MaskSlot, RecSlot) filled on another stream: after the fill, on the device,
+// until the host has seen the fill complete.
+template <class Slot>
+int wait_ready(Slot& s, hipStream_t st) {
+  if (s.seen_ready || s.fill_stream == st) return RT_OK;
+  if (hipEventQuery(s.ready) == hipSuccess) {
+    s.seen_ready = true;
+    return RT_OK;
+  }
+  (void)hipGetLastError();
+  RT_HIP(hipStreamWaitEvent(st, s.ready, 0));
+  return RT_OK;
+}
+// Runtime flags to template arguments: f(std::bool_constant / std::integral_constant values...).  The generic
+// row, deferred and view kernels are instantiated through these, each combination once.
+template <class F>
+void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <class F>
+void with_mode(int mode, F&& f) {
+  if (mode == RT_MODE_CHAIN) f(std::integral_constant<int, RT_MODE_CHAIN>{});
+  else if (mode == RT_MODE_TREE) f(std::integral_constant<int, RT_MODE_TREE>{});
+  else f(std::integral_constant<int, RT_MODE_REFL>{});
+}
+template <class F>
+void with_flags(bool f64, bool cal, bool fc, F&& f) {   // f(F64, CAL, FC)
+  with_bool(f64, [&](auto d) { with_bool(cal, [&](auto c) { with_bool(fc, [&](auto k) { f(d, c, k); }); }); });
+}
 // rt_ctx.hip
+// The order slot of a launch of n_tiles tiles with geometry `key` on st: null below RT_ORDER_MIN_TILES or with
+// the tile order off; *calibrate: the slot is new (its tables allocated, the costs zeroed on st) and this
+// launch measures it.  finish_calibration, after that launch (synchronous, once per geometry and scene
+// upload): costs -> order_from_costs -> the order on the device, the slot valid.
+int acquire_order(rt_ctx* c, const int32_t (&key)[8], size_t n_tiles, hipStream_t st, rt_ctx::OrderSlot** slot, bool* calibrate);
+int finish_calibration(rt_ctx* c, hipStream_t st, rt_ctx::OrderSlot* slot, const OrderParams& p);
+// The end of every row launch, behind its last kernel: the timing event, the completion mark where no kernel
+// carried it as its stop event (`mark`: the wavefront path), the copy to the caller's buffer when that is host
+// memory (the launch rendered into the context's scratch) and the wait for it.
+struct HostCopy { void* out; size_t stride; const uint8_t* src; size_t src_stride, row_bytes, n_rows; };   // out null: none
+int finish_launch(rt_ctx* c, hipStream_t st, const HostCopy& hc, bool mark);
 void drop_order(rt_ctx::OrderSlot& s);         // frees an order table (hipFree waits for its readers)
 void drop_orders(rt_ctx* c);
 void reset_order_choices(rt_ctx* c);           // a same-structure upload keeps the orders; the ray-tree wavefront choice is timed again
 // k_masks.hip: the tile-mask tables
 void drop_masks(rt_ctx* c);                    // every table (upload, free): hipFree waits for their readers
-// The table of the geometry (a0..a3 as launch_wavefront) for a launch on st, filled on st first if it is new
-// since the upload; *table = nullptr when the context takes no masks.
-// (*mslot: the table's slot, for launch_records)
-int launch_masks(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t n_tiles, const uint32_t** table,
-                 const void** mslot = nullptr);
+bool masks_usable(const rt_ctx* c);            // the uploaded scene has a mask scene (LaunchFacts::masks_ok)
+// The mask table's slot of the geometry (a0..a3 as launch_wavefront) for a launch on st, filled on st first if it
+// is new since the upload
+int mask_slot(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t n_tiles, rt_ctx::MaskSlot** out);
 // The dispatch records (RecSlot) of a launch of n_entries order entries (d_order of calibration order_id; null and
-// 0: the identity) whose mask table is mask_slot's, gathered on st first if the masks or the order are new.
-int launch_records(rt_ctx* c, hipStream_t st, const void* mask_slot, const int32_t* d_order, uint64_t order_id,
+// 0: the identity) whose mask table is ms's, gathered on st first if the masks or the order are new.
+int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const int32_t* d_order, uint64_t order_id,
                    uint32_t n_entries, const RtTileRec** table, const void** rslot = nullptr);
 void drop_records(rt_ctx* c);                  // every record table (upload, free)
 // How many of a record table's entries say sky (rslot as launch_records gave it, rec_id its RecSlot::rec_id);
@@ -215,10 +274,11 @@ bool diag_env(const char* name);
 // k_wavefront.hip: the wavefront path for rows (y_first, band_rows, band_pitch, n_rows) = a0..a3
 int launch_wavefront(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, int max_depth, uint8_t* target,
                      size_t tstride, bool f64, int rgbi, size_t n_tiles, int retry = 0);
-// k_stereo.hip: a two-eye scene's row launch (launch_bands' arguments after its checks; out / stride = the
-// caller's buffer when it is host memory, target the context's scratch then)
+// k_stereo.hip: a two-eye scene's row launch (launch_bands' arguments after its checks)
 int launch_views(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, int max_depth, uint8_t* target, size_t tstride,
-                 bool f64, int rgbi, void* host_out, size_t host_stride, size_t row_bytes);
+                 bool f64, int rgbi, const HostCopy& hc);
+// The facts of a row launch that the context holds (launch_bands and launch_views add the launch's own)
+LaunchFacts launch_facts(const rt_ctx* c, int max_depth, bool f64, size_t n_tiles, const rt_ctx::OrderSlot* slot, bool calibrate);
 // Completion marks (rt_ctx.hip): record one after every launch of the context on stream st; wait for all
 int mark_event(rt_ctx* c, hipStream_t st, hipEvent_t* ev);   // the event a launch on st binds as its stop event
 int mark_launch(rt_ctx* c, hipStream_t st);                  // record it after work enqueued on st (other launches)

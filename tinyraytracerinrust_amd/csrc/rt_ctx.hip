@@ -1,6 +1,7 @@
 // rt_ctx.hip -- the device context of the C ABI (include/rt_abi.h): device discovery, context
-// create / free, scene upload (rt::flatten -> one HBM blob, rt_blob.h), options, own-queue streams.
-// Host code only; the kernels and their launches live in k_rows.hip, k_wavefront.hip, k_views.hip.
+// create / free, scene upload (rt::flatten -> one HBM blob, rt_blob.h), options, own-queue streams, and what
+// the row launches share: the order slots (acquire_order, finish_calibration) and finish_launch.
+// Host code only; the kernels and their launches live in k_rows.hip, k_stereo.hip, k_wavefront.hip, k_views.hip.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -36,6 +37,71 @@ void drop_orders(rt_ctx* c) {
 // megakernel for ray-tree scenes (wf_tune), timed again by the next ordered launch of the geometry.
 void reset_order_choices(rt_ctx* c) {
   for (auto& s : c->order) s.wf_tune = 0;
+}
+
+// Tile order: reuse the measured order for this exact geometry, else calibrate on this launch.
+int acquire_order(rt_ctx* c, const int32_t (&key)[8], size_t n_tiles, hipStream_t st, rt_ctx::OrderSlot** out, bool* calibrate) {
+  *out = nullptr;
+  *calibrate = false;
+  if (!c->tile_order || n_tiles < RT_ORDER_MIN_TILES) return RT_OK;
+  bool found;
+  rt_ctx::OrderSlot* slot = find_slot(c->order, [&](const rt_ctx::OrderSlot& s) { return memcmp(s.key, key, sizeof key) == 0; }, &found);
+  if (!found) {                       // calibrate into the empty or least recently used slot
+    drop_order(*slot);
+    RT_HIP(hipMalloc((void**)&slot->d_order, n_tiles * sizeof(int32_t)));
+    RT_HIP(hipMalloc((void**)&slot->d_cost, n_tiles * sizeof(uint32_t)));
+    RT_HIP(hipMemsetAsync(slot->d_cost, 0, n_tiles * sizeof(uint32_t), st));   // tiles that store no cost sort last
+    memcpy(slot->key, key, sizeof key);
+    slot->n_tiles = n_tiles;
+    slot->grid = (uint32_t)n_tiles;
+    slot->order_id = ++c->order_ids;
+    *calibrate = true;
+  }
+  slot->last_use = ++c->use_clock;
+  *out = slot;
+  return RT_OK;
+}
+
+int finish_calibration(rt_ctx* c, hipStream_t st, rt_ctx::OrderSlot* slot, const OrderParams& p) {
+  const size_t n_tiles = slot->n_tiles;
+  std::vector<uint32_t> h_cost(n_tiles);
+  RT_HIP(hipMemcpyAsync(h_cost.data(), slot->d_cost, n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  RT_HIP(hipStreamSynchronize(st));
+  const TileOrder o = order_from_costs(h_cost, p);
+  slot->masks_pay = o.masks_pay;
+  slot->deferred = o.deferred;
+  if (o.entries.size() > n_tiles) {   // split tiles: more entries than the calibration's table holds
+    int32_t* d = nullptr;
+    RT_HIP(hipMalloc((void**)&d, o.entries.size() * sizeof(int32_t)));
+    (void)hipFree(slot->d_order);
+    slot->d_order = d;
+  }
+  slot->grid = (uint32_t)o.entries.size();
+  RT_HIP(hipMemcpyAsync(slot->d_order, o.entries.data(), o.entries.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  RT_HIP(hipStreamSynchronize(st));
+  slot->valid = true;
+  static const bool order_debug = diag_env("RT_TILE_ORDER_DEBUG");
+  if (order_debug) {                  // wave times in wall-clock ticks (100 MHz)
+    std::vector<uint32_t>& v = h_cost;
+    std::sort(v.begin(), v.end());
+    double sum = 0.0;
+    for (uint32_t x : v) sum += x;
+    fprintf(stderr, "tile order: %zu tiles, max %u, p99 %u, p90 %u, median %u, mean %.1f ticks; max / (sum / %.0f slots) = %.3f; "
+            "ordered launches: %s kernel, %u entries\n", n_tiles, v.back(), v[n_tiles * 99 / 100], v[n_tiles * 9 / 10],
+            v[n_tiles / 2], sum / n_tiles, p.slots, v.back() / (sum / p.slots), slot->deferred ? "deferred" : "mega", slot->grid);
+  }
+  return RT_OK;
+}
+
+int finish_launch(rt_ctx* c, hipStream_t st, const HostCopy& hc, bool mark) {
+  if (c->timing) RT_HIP(hipEventRecord(c->ev1, st));
+  c->timed = c->timing;
+  if (mark) RT_TRY(mark_launch(c, st));
+  if (hc.out) {
+    RT_HIP(hipMemcpy2DAsync(hc.out, hc.stride, hc.src, hc.src_stride, hc.row_bytes, hc.n_rows, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+  }
+  return RT_OK;
 }
 
 int ensure_scratch(rt_ctx* c, size_t bytes) {
