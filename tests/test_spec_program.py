@@ -172,10 +172,11 @@ def _fnv1a(b):
 
 
 def test_disk_cache_identity_covers_headers_and_options(tmp_path):
-    """the program text only #includes rt_device.h / rt_blob.h / rt_math.h, which the
-    library embeds, so the disk-cache identity must cover them (and the compile options): it ends in
-    "build H" with H = FNV-1a over the three embedded headers and the options, here recomputed from the
-    sources, and an entry written under another build's identity is recompiled, not read."""
+    """the program text only #includes the device headers (rt_device.h and its parts,
+    rt_blob.h, rt_math.h: the Makefile's SPEC_HDRS), which the library embeds, so the disk-cache identity
+    must cover them (and the compile options): it ends in "build H" with H = FNV-1a over every embedded
+    header, in the list's order, and the options, here recomputed from the sources, and an entry written
+    under another build's identity is recompiled, not read."""
     import subprocess
     import sys
     import tinyraytracerinrust_amd as T
@@ -183,10 +184,16 @@ def test_disk_cache_identity_covers_headers_and_options(tmp_path):
     ident, rocm = T.spec_compiler_info()
     m = re.search(r" build ([0-9a-f]{16})$", ident)
     assert m, ident
+    pkg = os.path.join(ROOT, "tinyraytracerinrust_amd")
+    hdrs = re.search(r"^SPEC_HDRS\s*:=\s*(.+)$", open(os.path.join(pkg, "Makefile")).read(), re.M).group(1).split()
+    assert len(hdrs) >= 3 and {"csrc/rt_device.h", "csrc/rt_blob.h", "csrc/rt_math.h"} <= set(hdrs), hdrs
     key = b""
-    for h in ("rt_device", "rt_blob", "rt_math"):
-        with open(os.path.join(ROOT, "tinyraytracerinrust_amd", "csrc", h + ".h"), "rb") as f:
-            key += f.read() + b"\0"
+    for h in hdrs:
+        with open(os.path.join(pkg, h), "rb") as f:
+            body = f.read()
+        key += body + b"\0"
+        for inc in re.findall(rb'^#include "(\w+\.h)"', body, re.M):     # a listed header includes listed headers only
+            assert "csrc/" + inc.decode() in hdrs, (h, inc)
     for o in ("--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mllvm",
               "-disable-machine-licm"):
         key += o.encode() + b"\0"

@@ -47,7 +47,7 @@ def test_every_entry_reads_its_own_tile(n, identity):
 def test_kernel_and_gather_agree_on_the_slot():
     """Writer and reader index the table by the order entry alone."""
     assert "out[e] = r;" in open(os.path.join(CSRC, "k_masks.hip")).read()
-    assert "as_const(recs) + entry;" in open(os.path.join(CSRC, "rt_device.h")).read()
+    assert "as_const(recs) + entry;" in open(os.path.join(CSRC, "rt_bodies.h")).read()   # rows_entry
 
 
 def test_option_constant_and_header_agree():

@@ -172,7 +172,7 @@ __device__ __forceinline__ void wf_ray_core(const DS& S, V3 ro, V3 rd, int depth
 template <bool REFR, bool FC>
 __device__ __forceinline__ void wf_ray(const DS& S, V3 ro, V3 rd, int depth, int max_depth, Col* Lo, double* wt,
                                        double* wr, bool* ch_t, bool* ch_r, V3* po, V3* dt, V3* dr, int* hit_obj) {
-  constexpr bool SHARE = REFR && RT_SPHERE_SHARE, OBB = !REFR;
+  constexpr bool SHARE = REFR, OBB = !REFR;
   wf_ray_core<REFR, FC>(
       S, ro, rd, depth, max_depth,
       [&](double* t) { return *hit_obj = nearest_hit<SHARE, OBB>(S, ro, rd, t); },
@@ -395,7 +395,7 @@ static_assert(RT_WFP_COUNT + 5 <= 64, "wavefront counter block: 256 bytes");
 // The object's nearest accepted distance for one ray: nearest_hit's body for one object, its best
 // starting at +inf (the leaf boxes' tmax only shrinks, as share_prev requires).
 __device__ __forceinline__ double wfp_object_nearest(const DS& S, int o, V3 ro, V3 rd, const CullR& cr) {
-  const bool cf_ok = RT_CONST_FILTER && const_filter_range(ro, rd);
+  const bool cf_ok = const_filter_range(ro, rd);
   cptr<RtObject> O = &S.objects[o];
   const bool fin = wave_finite(ro, rd);
   double best = INFINITY;
@@ -408,7 +408,7 @@ __device__ __forceinline__ double wfp_object_nearest(const DS& S, int o, V3 ro, 
       if (L->cull == RT_CULL_BOX && !RT_BOX_MAY_HIT(L, blo, bhi, cr, RT_CULL_TMAX(best))) continue;
     }
     double t0 = 0.0, t1 = 0.0;
-    const int n = leaf_candidates<true>(L, ro, rd, fin, &t0, &t1, RT_SPHERE_SHARE ? &shr : nullptr);
+    const int n = leaf_candidates<true>(L, ro, rd, fin, &t0, &t1, &shr);
     const bool filtered = L->prog_end != L->prog_begin && !(cf_ok && L->filter_const);
     if (n >= 1 && t0 > EPS && t0 < best && (!filtered || leaf_filter(S, L, add(ro, scale(rd, t0))))) best = t0;
     if (n >= 2 && t1 > EPS && t1 < best && (!filtered || leaf_filter(S, L, add(ro, scale(rd, t1))))) best = t1;
@@ -421,7 +421,7 @@ __device__ __forceinline__ double wfp_object_nearest(const DS& S, int o, V3 ro, 
 __device__ __forceinline__ uint32_t wfp_object_shadow(const DS& S, int o, V3 p, V3 dir, double dist, const CullR& cr) {
   cptr<RtObject> O = &S.objects[o];
   const bool fin = wave_finite(p, dir);
-  const bool cf_ok = RT_CONST_FILTER && const_filter_range(p, dir);
+  const bool cf_ok = const_filter_range(p, dir);
   const CullT tmax = RT_CULL_TMAX(dist);
   const bool zero = O->transparency == 0.0;
   uint32_t cnt = 0;
@@ -434,7 +434,7 @@ __device__ __forceinline__ uint32_t wfp_object_shadow(const DS& S, int o, V3 p, 
       if (L->cull == RT_CULL_BOX && !RT_BOX_MAY_HIT(L, blo, bhi, cr, tmax)) continue;
     }
     double t0 = 0.0, t1 = 0.0;
-    const int n = leaf_candidates<true>(L, p, dir, fin, &t0, &t1, RT_SPHERE_SHARE ? &shr : nullptr);
+    const int n = leaf_candidates<true>(L, p, dir, fin, &t0, &t1, &shr);
     const bool filtered = L->prog_end != L->prog_begin && !(cf_ok && L->filter_const);
     if (n >= 1 && t0 > EPS && t0 < dist && (!filtered || leaf_filter(S, L, add(p, scale(dir, t0))))) {
       ++cnt;
@@ -855,11 +855,6 @@ using namespace rt;
 extern "C" hipError_t rt_wf_bucket_sort(const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in,
                                         uint32_t* vals_out, uint32_t n, const uint32_t* n_dev, uint32_t nb, int shift,
                                         uint32_t* cnt, bool zero_cnt, hipStream_t stream, bool counted = false);
-#ifdef RT_WF_RADIX_SORT
-extern "C" hipError_t rt_wf_sort_pairs(void* d_temp, size_t* temp_bytes, const uint32_t* keys_in, uint32_t* keys_out,
-                                       const uint32_t* vals_in, uint32_t* vals_out, int n, int end_bit,
-                                       hipStream_t stream);
-#endif
 #define RT_WF_LEVEL_BINS 4096u          // bucket-sort bins of a non-pair level (the key's top 12 bits)
 
 // Pair-path arrays (above, "wavefront pair path"): per ray of a level (R = the larger of
@@ -1009,13 +1004,7 @@ int rt::launch_wavefront(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int 
   if (cap > 0x7fffffffull || slots > 0x7fffffffull) return fail(RT_ERR_UNSUPPORTED, "wavefront launch of %zu pixel slots too large", slots);
   // the non-pair levels' coherence order: the in-tree bucket sort on the key's top 12 bits (direction
   // octant + the 8^3-cell Morton prefix); only the processing order depends on it, never a value
-  // (diagnostic builds with RT_WF_RADIX_SORT: the full 30-bit rocPRIM radix sort it replaced)
-#ifdef RT_WF_RADIX_SORT
-  size_t sort_bytes = 0;
-  RT_HIP(rt_wf_sort_pairs(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, (int)cap, 30, st));
-#else
   const size_t sort_bytes = RT_WF_LEVEL_BINS * 4;
-#endif
   const size_t levels = slots * RT_WF_BYTES0 + (size_t)max_depth * cap * RT_WF_BYTES;
   const size_t o_cnt = (levels + 255) & ~(size_t)255, o_ovf = o_cnt + 256, o_kout = (o_ovf + slots + 255) & ~(size_t)255;
   const size_t o_perm = o_kout + cap * 4, o_tmp = (o_perm + cap * 4 + 255) & ~(size_t)255, bytes = o_tmp + sort_bytes + 256;
@@ -1080,12 +1069,7 @@ int rt::launch_wavefront(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int 
     }
     if (d > 0) {                                             // this level's slots in key order
       const WfLevel L = wf_level(A, d);                      // host-side pointer arithmetic only
-#ifdef RT_WF_RADIX_SORT
-      size_t tb = sort_bytes;
-      RT_HIP(rt_wf_sort_pairs(tmp, &tb, L.key, kout, L.val, perm, (int)n, 30, st));
-#else
       RT_HIP(rt_wf_bucket_sort(L.key, kout, L.val, perm, n, nullptr, RT_WF_LEVEL_BINS, 30 - 12, (uint32_t*)tmp, true, st));
-#endif
       A.perm = perm;
     }
     const dim3 g((n + 63) / 64);

@@ -19,7 +19,7 @@
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <stdint.h>
-#else                                // hipRTC (spec.hip): its runtime header keeps these in a namespace
+#else                                // hipRTC (the specialised programs): its runtime header keeps these in a namespace
 using __hip_internal::int32_t;
 using __hip_internal::int64_t;
 using __hip_internal::uint8_t;

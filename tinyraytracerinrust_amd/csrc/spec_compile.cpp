@@ -19,7 +19,8 @@
 
 namespace {
 
-// The device headers as text (build/spec_headers.inc: raw string literals made by the Makefile).
+// The device headers as text: spec_headers[], {name, text} pairs in the order of the Makefile's SPEC_HDRS
+// (build/spec_headers.inc: raw string literals made by the Makefile).
 #include "spec_headers.inc"
 
 // The hipRTC the programs compile with: the ROCm installation's own (ROCM_PATH, default /opt/rocm),
@@ -169,8 +170,8 @@ void code_resources(SpecCode* c) {
 // a kernel argument) changes the identity, so an entry written by another build is never read.
 std::string spec_build_identity() {
   std::string key;
-  for (const char* h : {spec_hdr_rt_device, spec_hdr_rt_blob, spec_hdr_rt_math}) {
-    key += h;
+  for (const auto& h : spec_headers) {
+    key += h.text;
     key += '\0';
   }
   for (const std::string& o : spec_options()) {
@@ -185,11 +186,14 @@ std::string spec_build_identity() {
 // hipRTC: the program (with the device headers as named headers), spec_options(), and the resource use
 // the guard reads from the code object.
 int spec_compile(const std::string& src, SpecCode* out, std::string* err) {
-  const char* headers[] = {spec_hdr_rt_device, spec_hdr_rt_blob, spec_hdr_rt_math};
-  const char* names[] = {"rt_device.h", "rt_blob.h", "rt_math.h"};
+  std::vector<const char*> headers, names;
+  for (const auto& h : spec_headers) {
+    headers.push_back(h.text);
+    names.push_back(h.name);
+  }
   hiprtcProgram prog;
   const Rtc& R = rtc();
-  if (R.create(&prog, src.c_str(), "rt_spec.hip", 3, headers, names) != HIPRTC_SUCCESS) {
+  if (R.create(&prog, src.c_str(), "rt_spec.hip", (int)headers.size(), headers.data(), names.data()) != HIPRTC_SUCCESS) {
     *err = "hiprtcCreateProgram failed";
     return RT_ERR_DEVICE;
   }

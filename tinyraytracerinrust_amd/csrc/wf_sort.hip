@@ -1,23 +1,9 @@
 // wf_sort.hip -- the wavefront path's orderings (k_wavefront.hip): the in-tree bucket sort below
 // orders the pair path's (object, pair) lists, its hit points, and the non-pair levels' rays by the
-// top 12 bits of their coherence key.  (Diagnostic builds with RT_WF_RADIX_SORT keep the rocPRIM radix
-// sort through hipCUB the non-pair levels used before round 4, for A/B runs.)
+// top 12 bits of their coherence key.
 #include <hip/hip_runtime.h>
-#ifdef RT_WF_RADIX_SORT
-#include <hipcub/hipcub.hpp>
-#endif
 #include <stdint.h>
 #include <algorithm>
-
-#ifdef RT_WF_RADIX_SORT
-// d_temp == nullptr: *temp_bytes = the scratch the sort of n pairs needs.  Sorts bits [0, end_bit).
-extern "C" hipError_t rt_wf_sort_pairs(void* d_temp, size_t* temp_bytes, const uint32_t* keys_in, uint32_t* keys_out,
-                                       const uint32_t* vals_in, uint32_t* vals_out, int n, int end_bit,
-                                       hipStream_t stream) {
-  return hipcub::DeviceRadixSort::SortPairs(d_temp, *temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0, end_bit,
-                                            stream);
-}
-#endif
 
 // ---------------------------------------------------------------------------- bucket sort
 // The pair path's sort of (object, pair) by object: few keys (the scene's objects), many items.  A
