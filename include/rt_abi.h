@@ -370,6 +370,17 @@ int rt_ctx_synchronize(rt_ctx* ctx);
  * rt_ctx_kernel_info says "; sky fill: off" or "; sky fill: on (N render, M sky entries)" for the last launch,
  * ahead of "; last launch: ..." (the counts come from a pinned host word the records' gather fills; the call
  * never waits, and says "on (counts pending)" until that gather has completed).
+ * RT_OPT_LEAN_TILES: 1 (default) the entries of a megakernel launch in whose tile every ray up to the depth-1
+ * nearest hit can meet the mask plane alone -- the prim word, the shadow words of the scene's lights and the refl
+ * word hold no other object -- are rendered by a lean kernel of the same program (one plane hit, its lights, one
+ * fold; 8 waves per SIMD) launched ahead of the megakernel on the same stream, and the megakernel's waves of
+ * those entries return at once.  The class is decided once per record table: the gather marks the candidates,
+ * and a check kernel behind it, built from the lean kernel's own functions, clears every entry in which some
+ * pixel's reflected ray would hit anything (the plane's own leaf test still runs on that ray).  Only programs of
+ * reflection-only scenes with a mask plane, every other object boxed and at most 4 lights hold the kernels, and
+ * only non-calibrating megakernel launches that read records take them.  0: no record says lean.  Same pixels.
+ * rt_ctx_kernel_info says "; lean tiles: off" or "; lean tiles: on (N entries)" ahead of "; sky fill: ..."
+ * ("on (count pending)" until the table's check has completed; the call never waits).
  * Two-eye scenes (rt_scene_set_camera_kind) always take the view megakernels (k_stereo.hip: one launch over
  * the tiles of both eyes, mask-free walks): RT_KERNEL_DEFERRED, RT_KERNEL_WAVEFRONT and RT_OPT_TILE_MASKS have
  * no effect on them; RT_OPT_TILE_ORDER and RT_OPT_SPECIALIZE apply (rt_ctx_kernel_info says which kernel ran).
@@ -386,7 +397,7 @@ int rt_ctx_synchronize(rt_ctx* ctx);
 typedef enum rt_option {
   RT_OPT_KERNEL = 0, RT_OPT_TIMING = 1, RT_OPT_TILE_ORDER = 2, RT_OPT_FAST_CLAMP = 3, RT_OPT_WAVEFRONT_CAP = 4,
   RT_OPT_WAVEFRONT_PAIRS = 5, RT_OPT_SPECIALIZE = 6, RT_OPT_TILE_MASKS = 8, RT_OPT_SPEC_SAMPLES = 9,
-  RT_OPT_TILE_RECORDS = 10, RT_OPT_SKY_FILL = 11
+  RT_OPT_TILE_RECORDS = 10, RT_OPT_SKY_FILL = 11, RT_OPT_LEAN_TILES = 12
 } rt_option;
 typedef enum rt_kernel_choice {
   RT_KERNEL_AUTO = 0, RT_KERNEL_MEGA = 1, RT_KERNEL_DEFERRED = 2, RT_KERNEL_WAVEFRONT = 3
@@ -428,6 +439,9 @@ int rt_ctx_sample_kernel_info(rt_ctx* ctx, char* buf, size_t cap);
  * the row programs: one line per kernel (rt_spec_points, rt_spec_aa) in that call's "NAME: field value ..."
  * format.  RT_ERR_UNSUPPORTED: a scene above the specialisation limits, or a two-eye scene. */
 int rt_scene_sample_report(const rt_scene* scene, char* buf, size_t cap, size_t* len);
+/* The same for the lean kernels (RT_OPT_LEAN_TILES: rt_spec_lean_0, rt_spec_lean_check), which a context's row
+ * programs include and rt_scene_spec_report does not list; no lines for a scene whose programs hold none. */
+int rt_scene_lean_report(const rt_scene* scene, char* buf, size_t cap, size_t* len);
 /* Compile the scene's specialised program (RT_OPT_SPECIALIZE) into the process's code-object
  * cache without a device, so a later upload of the same scene finds it; *compile_ms = the hipRTC
  * time (0 when it was cached already).  May run on any thread. */

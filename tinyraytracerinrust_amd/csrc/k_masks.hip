@@ -31,8 +31,8 @@ __global__ __launch_bounds__(64) void tile_masks_kernel(const RtTileMaskScene* _
 // (order[e], or e without an order) from the tile-indexed mask table.
 __global__ __launch_bounds__(64) void tile_records_kernel(const uint32_t* __restrict__ masks, const int32_t* __restrict__ order,
                                                           uint32_t n_entries, uint32_t n_tiles, uint32_t tiles_x,
-                                                          uint32_t keep_bit, RtTileRec* __restrict__ out,
-                                                          uint32_t* __restrict__ n_sky) {
+                                                          uint32_t keep_bit, int lean_lights, uint32_t plane_bit,
+                                                          RtTileRec* __restrict__ out, uint32_t* __restrict__ n_sky) {
   const uint32_t e = blockIdx.x * 64u + threadIdx.x;
   bool sky = false;
   if (e < n_entries) {
@@ -47,10 +47,33 @@ __global__ __launch_bounds__(64) void tile_records_kernel(const uint32_t* __rest
     // node ignores the mask) and which only ever makes a word looser.
     if (r.mask[0] == 0) r.mask[0] = keep_bit;
     sky = r.mask[0] == 0;
+    // A lean candidate (RT_OPT_LEAN_TILES; lean_lights < 0: off): the tile is not sky, and its prim word, the
+    // shadow words of the scene's lean_lights lights and its refl word hold no object but the mask plane (a word
+    // the predicate gave up on is all ones).  The sign of x0 says so; the check behind this kernel
+    // (launch_records) has the last word.
+    bool lean = lean_lights >= 0 && !sky && tile < n_tiles && (r.mask[0] & ~plane_bit) == 0 && (r.mask[5] & ~plane_bit) == 0;
+    for (int l = 0; l < lean_lights && l < 4; ++l) lean = lean && (r.mask[1 + l] & ~plane_bit) == 0;
+    if (lean) r.x0 |= (int32_t)0x80000000u;
     out[e] = r;
   }
   const unsigned long long b = __ballot(sky);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_sky, (uint32_t)__popcll(b));
+}
+
+// The entries of a checked record table that kept the lean bit, counted as the gather counts the sky entries
+// (atomics per wave of 64 entries): out[0] their number, out[1] the maximum of ~e, out[2] the maximum of e + 1
+// (zeroed by the caller: the run [~out[1], out[2]) holds them all).
+__global__ __launch_bounds__(64) void lean_count_kernel(const RtTileRec* __restrict__ recs, uint32_t n_entries,
+                                                        uint32_t* __restrict__ out) {
+  const uint32_t e = blockIdx.x * 64u + threadIdx.x;
+  const bool lean = e < n_entries && recs[e].x0 < 0;
+  const unsigned long long b = __ballot(lean);
+  if ((threadIdx.x & 63) == 0 && b) {
+    const uint32_t base = blockIdx.x * 64u;
+    atomicAdd(out, (uint32_t)__popcll(b));
+    atomicMax(out + 1, ~(base + (uint32_t)__builtin_ctzll(b)));
+    atomicMax(out + 2, base + 64u - (uint32_t)__builtin_clzll(b));
+  }
 }
 
 bool finite3(const double* p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
@@ -306,6 +329,13 @@ bool tilemask_sky_ok(const FlatScene& f) {
   return true;
 }
 
+// Lean tiles (RT_OPT_LEAN_TILES): a record may say lean only where the mask plane is the one unbounded object
+// (every walk under a word without boxed objects then visits the plane alone) and the record's four shadow
+// words cover the scene's lights; the specialised programs hold the kernels for such scenes only (LEAN_OK).
+bool tilemask_lean_ok(const FlatScene& f) {
+  return tilemask_sky_ok(f) && !f.any_transparent && f.lights.size() <= RT_TILEMASK_LIGHTS;
+}
+
 // rt_scene_describe's lines on the tile masks' bounds: per boxed object its vertex sets and whether it has a ball
 std::string describe_tile_bounds(const FlatScene& f) {
   RtTileMaskScene t;
@@ -341,22 +371,25 @@ bool masks_usable(const rt_ctx* c) {
 // else gathered on st, behind the mask fill: mask_slot has put the fill, or a wait for its event, on st
 // already.  Launches on other streams wait for the gather's own event.
 int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const int32_t* d_order, uint64_t order_id,
-                   uint32_t n_entries, const RtTileRec** table, const void** rslot) {
+                   uint32_t n_entries, bool lean, const RtTileRec** table, const void** rslot) {
   *table = nullptr;
   if (rslot) *rslot = nullptr;
   const bool sky_fill = c->sky_fill && c->sky_ok;
   bool found;
   rt_ctx::RecSlot* slot = find_slot(c->recs, [&](const rt_ctx::RecSlot& s) {
-    return s.fill_id == ms->fill_id && s.order_id == order_id && s.n_entries == n_entries && s.sky_fill == sky_fill;
+    return s.fill_id == ms->fill_id && s.order_id == order_id && s.n_entries == n_entries && s.sky_fill == sky_fill &&
+           s.lean == lean;
   }, &found);
   if (!found) {
     drop_rec(*slot);
-    // (one more record's room behind the table: the count of sky entries, for rt_ctx_kernel_info)
+    // (one more record's room behind the table: the counts of sky and lean entries, for rt_ctx_kernel_info, and
+    // the lean entries' run, for their kernel's grid)
     RT_HIP(hipMalloc((void**)&slot->d_recs, ((size_t)n_entries + 1) * sizeof(RtTileRec)));
     slot->d_sky = (uint32_t*)(slot->d_recs + n_entries);
-    RT_HIP(hipMemsetAsync(slot->d_sky, 0, sizeof(uint32_t), st));
-    RT_HIP(hipHostMalloc((void**)&slot->h_sky, sizeof(uint32_t), hipHostMallocDefault));
-    *slot->h_sky = 0;
+    RT_HIP(hipMemsetAsync(slot->d_sky, 0, 4 * sizeof(uint32_t), st));
+    RT_HIP(hipHostMalloc((void**)&slot->h_sky, 4 * sizeof(uint32_t), hipHostMallocDefault));
+    memset(slot->h_sky, 0, 4 * sizeof(uint32_t));
+    slot->lean = lean;
     slot->rec_id = ++c->rec_ids;
     slot->sky_fill = sky_fill;
     RT_HIP(hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming));
@@ -366,9 +399,21 @@ int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const 
     const uint32_t tiles_x = (uint32_t)((c->dev.width + RT_TILE_W - 1) / RT_TILE_W);
     hipLaunchKernelGGL(tile_records_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, st, (const uint32_t*)ms->d_masks, d_order,
                        n_entries, (uint32_t)ms->n_tiles, tiles_x,
-                       sky_fill || c->mask_plane < 0 ? 0u : 1u << c->mask_plane, slot->d_recs, slot->d_sky);
+                       sky_fill || c->mask_plane < 0 ? 0u : 1u << c->mask_plane, lean ? c->dev.n_lights : -1,
+                       c->mask_plane < 0 ? 0u : 1u << c->mask_plane, slot->d_recs, slot->d_sky);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipMemcpyAsync(slot->h_sky, slot->d_sky, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (lean) {
+      // the check (rt_bodies.h lean_check_body): the program's own kernel over every entry, behind the gather;
+      // it clears the bit where a reflected ray would hit; the entries that keep it are counted behind it
+      const int a0 = ms->key[0], a1 = ms->key[1], a2 = ms->key[2], a3 = ms->key[3];
+      RtTileRec* d_recs = slot->d_recs;
+      void* kargs[] = {&c->dev, (void*)&a0, (void*)&a1, (void*)&a2, (void*)&a3, &d_recs};
+      RT_HIP(hipModuleLaunchKernel(spec_fn(c, SPEC_LEAN_CHECK, false, false), n_entries, 1, 1, 64, 1, 1, 0, st, kargs, nullptr));
+      hipLaunchKernelGGL(lean_count_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, st, (const RtTileRec*)slot->d_recs, n_entries,
+                         slot->d_sky + 1);
+      RT_HIP(hipGetLastError());
+    }
+    RT_HIP(hipMemcpyAsync(slot->h_sky, slot->d_sky, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     RT_HIP(hipEventRecord(slot->ready, st));
     slot->fill_stream = st;
     slot->valid = true;
@@ -392,6 +437,31 @@ int64_t record_sky_entries(rt_ctx* c, const void* rslot, uint64_t rec_id, uint32
   }
   *n_entries = slot->n_entries;
   return (int64_t)*slot->h_sky;
+}
+
+// The same for the entries that say lean once the table's check has run (a table gathered without them: 0).
+int64_t record_lean_entries(rt_ctx* c, const void* rslot, uint64_t rec_id) {
+  uint32_t n = 0;
+  const int64_t rc = record_sky_entries(c, rslot, rec_id, &n);
+  return rc < 0 ? rc : (int64_t)((const rt_ctx::RecSlot*)rslot)->h_sky[1];
+}
+
+bool record_lean_range(const void* rslot, uint32_t* first, uint32_t* end) {
+  rt_ctx::RecSlot* slot = (rt_ctx::RecSlot*)rslot;     // (the launch's own slot, as launch_records gave it)
+  if (!slot || !slot->valid || !slot->lean) return false;
+  if (!slot->seen_ready) {
+    if (hipEventQuery(slot->ready) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    slot->seen_ready = true;
+  }
+  const uint32_t n = slot->h_sky[1], lo = ~slot->h_sky[2], hi = slot->h_sky[3];
+  if (n == 0) { *first = *end = 0; return true; }
+  if (!(lo < hi && hi <= slot->n_entries)) return false;   // (never: the words are this table's)
+  *first = lo;
+  *end = hi;
+  return true;
 }
 
 }  // namespace rt

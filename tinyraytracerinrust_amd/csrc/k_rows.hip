@@ -59,6 +59,8 @@ LaunchFacts rt::launch_facts(const rt_ctx* c, int max_depth, bool f64, size_t n_
   f.has_rows_ordered = spec_fn(c, SPEC_ROWS, f64, false) != nullptr;
   f.sh_trcap = RT_SH_TRCAP; f.split_tile_mask = RT_SPLIT_TILE_MASK;
   f.refl_pooled = RT_LDS_POOL_REFL > 0; f.pool_byte_index = RT_POOL_OBJ_INDEX != 0;
+  f.lean_tiles = c->lean_tiles;
+  f.has_lean = spec_fn(c, SPEC_LEAN, f64, false) != nullptr && spec_fn(c, SPEC_LEAN_CHECK, false, false) != nullptr;
   return f;
 }
 
@@ -79,6 +81,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   (void)spec_poll(c);                     // the scene-specialised kernels, once their background compile is done
   c->last_masked = false;
   c->last_records = false;
+  c->last_lean_slot = nullptr;
   // a host buffer: render into the context's scratch, copy back at the end (finish_launch)
   uint8_t* target = (uint8_t*)out;
   size_t tstride = stride;
@@ -108,7 +111,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   const RtTileRec* recs = nullptr;
   const void* rec_slot = nullptr;
   if (plan.masks) RT_TRY(mask_slot(c, st, a0, a1, a2, a3, n_tiles, &ms));
-  if (plan.records) RT_TRY(launch_records(c, st, ms, order, order ? slot->order_id : 0, grid.x, &recs, &rec_slot));
+  if (plan.records) RT_TRY(launch_records(c, st, ms, order, order ? slot->order_id : 0, grid.x, plan.lean, &recs, &rec_slot));
   const uint32_t* masks = ms ? ms->d_masks : nullptr;
   c->last_masked = plan.masks;
   c->last_records = plan.records;
@@ -119,6 +122,8 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   }
   c->last_sky_slot = plan.sky ? rec_slot : nullptr;
   c->last_sky_id = plan.sky ? record_id(rec_slot) : 0;
+  c->last_lean_slot = plan.lean ? rec_slot : nullptr;
+  c->last_lean_id = plan.lean ? record_id(rec_slot) : 0;
   // the row kernels carry the context's completion event for this stream as their stop event
   hipEvent_t mev = nullptr;
 #ifndef RT_DIAG_NO_MARKS
@@ -130,6 +135,23 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
                      (void*)&order, &cost, (void*)&rgbi, (void*)&masks, (void*)&recs};   // (a kernel reads as
     // many as it declares: the masked single-scene kernels take the records, spec_text.cpp)
     // hipExtModuleLaunchKernel takes the global work size in work-items (grid x 64)
+    // the lean kernel first, over the same entries and operands: it renders the entries whose record says lean,
+    // the megakernel's waves of those return at entry (inside the frame's timing pair; the completion event stays
+    // the megakernel's)
+    // Its grid: the lean entries are the cheap end of the cost order, one run of entries holds them all; once the
+    // table's check has completed the host knows that run (a pinned word, never a wait) and the kernel is launched
+    // over it alone -- the table's address moved to the run's first record, the kernel unchanged.  Until then:
+    // every entry, the others' waves return at once.
+    if (plan.lean) {
+      uint32_t first = 0, end = grid.x;
+      (void)record_lean_range(rec_slot, &first, &end);
+      const RtTileRec* lean_recs = recs + first;
+      void* largs[] = {&c->dev, (void*)&a0, (void*)&a1, (void*)&a2, (void*)&a3, &max_depth, &target, &tstride,
+                       (void*)&order, &cost, (void*)&rgbi, (void*)&masks, (void*)&lean_recs};
+      if (end > first)
+        RT_HIP(hipExtModuleLaunchKernel(spec_fn(c, SPEC_LEAN, f64, false), (end - first) * 64u, 1, 1, 64, 1, 1, 0, st, largs,
+                                        nullptr, nullptr, nullptr, 0));
+    }
     RT_HIP(hipExtModuleLaunchKernel(spec_fn(c, plan.kind, f64, calibrate), grid.x * 64u, 1, 1, 64, 1, 1, 0, st, kargs,
                                     nullptr, nullptr, mev, 0));
   } else {

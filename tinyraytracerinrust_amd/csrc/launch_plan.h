@@ -100,6 +100,8 @@ struct LaunchFacts {
   uint32_t split_tile_mask;       // RT_SPLIT_TILE_MASK
   bool refl_pooled;               // RT_LDS_POOL_REFL > 0
   bool pool_byte_index;           // RT_POOL_OBJ_INDEX
+  // lean tiles: RT_OPT_LEAN_TILES, and the program holds the lean kernel for this f64 and its check
+  bool lean_tiles = false, has_lean = false;
 };
 
 struct LaunchPlan {
@@ -115,6 +117,8 @@ struct LaunchPlan {
   const char* last_kernel;        // rt_ctx_kernel_info's words
   // for the calibration this launch ends with (order_from_costs)
   bool defer_forced, defer_if_tail;
+  // the records carry checked lean bits, and the program's lean kernel runs ahead of the megakernel
+  bool lean = false;
 };
 
 inline LaunchPlan plan_row_launch(const LaunchFacts& f) {
@@ -190,6 +194,10 @@ inline LaunchPlan plan_row_launch(const LaunchFacts& f) {
   p.records = p.masks && f.tile_records && !(ordered && f.slot_deferred);
   // (a calibrating kernel renders every tile: cost[tile] is a tile's full time)
   p.sky = p.records && !calibrate && f.sky_fill && f.sky_ok;
+  // Lean tiles: a megakernel launch of the masked program that reads records and does not calibrate (the
+  // calibrating and the primary-ray kernels hold no exit for the bit, so their tables never carry it; a deferred
+  // or mask-free launch reads no records at all).
+  p.lean = f.lean_tiles && f.has_lean && p.path == LaunchPlan::MEGA && p.kind == SPEC_ROWS && p.records && !calibrate;
   // a megakernel launch without a table runs the program's mask-free megakernel (SPEC_ROWS_NOMASK)
   if (p.kind == SPEC_ROWS && !p.masks && f.has[SPEC_ROWS_NOMASK]) p.kind = SPEC_ROWS_NOMASK;
   // With the scene-specialised megakernel loaded for these launches its costliest tiles finish so

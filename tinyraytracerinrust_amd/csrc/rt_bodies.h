@@ -185,6 +185,14 @@ __device__ __forceinline__ void rows_entry(const RtDevScene& S, unsigned entry, 
     // words.  The records hold the launch's order; a calibrating launch has none (entry e is tile e).
     const cptr<RtTileRec> R = as_const(recs) + entry;
     tile = entry;
+#if defined(RT_SPEC) && RT_TILE_MASKS
+    // A lean tile (RT_OPT_LEAN_TILES; lean_body below): the record's x0 carries the sign bit, and the lean kernel
+    // launched ahead of this one renders the entry.  At kernel entry, next to the sky branch; not in the
+    // calibrating kernels (cost[tile] stays a tile's full time) nor the primary-ray kernel, whose launches'
+    // tables never carry the bit (launch_plan.h).
+    if constexpr (rt_spec::LEAN_OK && !CAL && !PRIM && MODE == RT_MODE_REFL)
+      if (R->x0 < 0) return;
+#endif
     x = R->x0 + lane % RT_TILE_W;
     r = R->r0 + lane / RT_TILE_W;
     for (int k = 0; k < RT_TILEMASK_WORDS; ++k) tm.w[k] = R->mask[k];
@@ -230,6 +238,87 @@ __device__ __forceinline__ void rows_body(const RtDevScene& S, int y_first, int 
   rows_entry<MODE, F64, CAL, FC, KL_, KP_, PRIM>(S, blockIdx.x, y_first, band_rows, band_pitch, n_rows, max_depth, out,
                                                  stride, order, cost, rgb, frames, masks, recs);
 }
+#if defined(RT_SPEC) && RT_TILE_MASKS
+// Lean tiles (RT_OPT_LEAN_TILES; DESIGN.md "Lean tiles"): an entry whose prim word, the shadow words of the scene's
+// lights and refl word hold no object but the mask plane, in a scene whose every other object is boxed
+// (rt_spec::LEAN_OK).  Every walk of such a tile up to the depth-1 nearest hit visits the plane alone, exactly as
+// under a mask of 0, so a pixel is trace<false>'s first iteration with that mask -- the plane hit, its lights
+// (hit_lights), the inside test -- and its reflected ray, the same functions inlined on the same values: the
+// same bits.  The reflected ray starts ON the plane and the plane's own leaf test still runs on it; whether it
+// ever accepts a hit is not argued from rounding but CHECKED: lean_check_body runs this function's CHECK form
+// (no lights, no store; the depth-1 walk kept) over the candidate entries once per record table and clears the
+// bit of any entry in which a lane's reflected ray hits.  In the entries that keep it the ray misses, its
+// colour is BLACK, and the render form folds the one frame as trace() does without walking.
+// CHECK: true when the pixel's reflected ray hits something.
+template <bool FC, bool CHECK>
+__device__ __forceinline__ bool lean_pixel(const DS& ds, V3 ro, V3 rd, int max_depth, Col* C) {
+  constexpr bool SHARE = false, OBB = true;                                // trace<false>'s walks
+  double t_hit;
+  const int oi = nearest_hit<SHARE, OBB>(ds, ro, rd, &t_hit, 0u);
+  *C = {0.0, 0.0, 0.0};                                                    // Color::BLACK
+  if (oi < 0) return false;
+  const V3 p = add(ro, scale(rd, t_hit));
+  V3 nrm = {0.0, 0.0, 0.0};
+  Col c = {0.0, 0.0, 0.0}, L = {0.0, 0.0, 0.0};
+  double transp = 0.0, refl = 0.0, nlen = 0.0;
+  if constexpr (CHECK) shade_inputs(ds, oi, p, &nrm, &c, &transp, &refl, &nlen);
+  else L = hit_lights<FC, SHARE, OBB>(ds, oi, p, 0u, &nrm, &c, &transp, &refl, &nlen);
+  // trace<false> at depth 0: rp = refl, a reflection where depth < max_depth, rp != 0 and the hit is seen from outside
+  const bool spawn = max_depth > 0 && refl != 0.0 && !hit_inside(rd, nrm, nlen);
+  if (!spawn) {
+    *C = L;
+    return false;
+  }
+  if constexpr (CHECK) {
+    double t1;
+    return nearest_hit<SHARE, OBB>(ds, p, reflect_dir(rd, nrm), &t1, 0u) >= 0;
+  }
+  *C = cadd<FC>(intensify<FC>(L, 1.0 - refl), intensify<FC>(Col{0.0, 0.0, 0.0}, refl));   // the frame, folded with BLACK
+  return false;
+}
+// The lean kernel's body: the megakernel's record load, guards, band_row and store over the same grid; an
+// entry that is not lean returns at once (the megakernel renders it).
+template <bool F64, bool FC>
+__device__ __forceinline__ void lean_body(const RtDevScene& S, int y_first, int band_rows, int band_pitch, int n_rows,
+                                          int max_depth, uint8_t* __restrict__ out, size_t stride, int rgb,
+                                          const RtTileRec* __restrict__ recs) {
+  const int lane = threadIdx.x & 63;
+  const cptr<RtTileRec> R = as_const(recs) + blockIdx.x;
+  const int x0 = R->x0;
+  if (x0 >= 0) return;
+  const int x = (x0 & 0x7fffffff) + lane % RT_TILE_W, r = R->r0 + lane / RT_TILE_W;
+  if (x >= S.width || r >= n_rows) return;
+  const int y = band_row(r, y_first, band_rows, band_pitch, n_rows);
+  if (y >= S.height) return;
+  V3 ro, rd;
+  camera_ray_px(S, x, y, &ro, &rd);
+  Col c;
+  lean_pixel<FC, false>(make_ds(S), ro, rd, max_depth, &c);
+  store_pixel<F64>(out + (size_t)r * stride, x, c, rgb);
+}
+// The check (k_masks.hip launch_records, behind the gather and ahead of the table's `ready` event): one wave
+// per entry; a candidate entry in which any valid pixel's reflected ray hits loses its bit.
+template <bool FC>
+__device__ __forceinline__ void lean_check_body(const RtDevScene& S, int y_first, int band_rows, int band_pitch, int n_rows,
+                                                RtTileRec* __restrict__ recs) {
+  const int lane = threadIdx.x & 63;
+  const int x0 = recs[blockIdx.x].x0, r0 = recs[blockIdx.x].r0;
+  if (__builtin_amdgcn_readfirstlane(x0) >= 0) return;
+  const int x = (x0 & 0x7fffffff) + lane % RT_TILE_W, r = r0 + lane / RT_TILE_W;
+  bool hit = false;
+  if (x < S.width && r < n_rows) {
+    const int y = band_row(r, y_first, band_rows, band_pitch, n_rows);
+    if (y < S.height) {
+      V3 ro, rd;
+      camera_ray_px(S, x, y, &ro, &rd);
+      Col c;
+      hit = lean_pixel<FC, true>(make_ds(S), ro, rd, 1, &c);
+    }
+  }
+  if (__ballot(hit) != 0 && lane == 0) recs[blockIdx.x].x0 = x0 & 0x7fffffff;   // vector store
+}
+#endif
+
 // Two-eye cameras (StereoscopicCamera / AnaglyphCamera, camera.rs:82-205; rt_blob.h RtViews): one launch
 // over the tiles of two views.  Entry e (or the order's e-th) is tile e of view 0 for e < tiles0, else
 // tile e - tiles0 of view 1; the wave's camera and column table are its view's (wave-uniform), the rows

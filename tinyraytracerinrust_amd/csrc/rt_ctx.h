@@ -112,6 +112,9 @@ struct rt_ctx {
     uint32_t* h_sky = nullptr;        //   to this pinned host word ahead of `ready` (rt_ctx_kernel_info reads it
     uint64_t rec_id = 0;              //   once hipEventQuery says so, never waiting); rec_id: never reused
     bool sky_fill = false;            // gathered with RT_OPT_SKY_FILL on for a scene that can have sky tiles
+    bool lean = false;                // gathered with the lean bits and checked (RT_OPT_LEAN_TILES); the entries that
+                                      //   kept theirs follow the sky count: d_sky / h_sky [1] their number, [2] ~first
+                                      //   entry, [3] last entry + 1 (both 0: none)
     uint32_t n_entries = 0;           // order entries = records
     uint64_t last_use = 0;
     hipStream_t fill_stream = nullptr;
@@ -132,6 +135,12 @@ struct rt_ctx {
   int mask_plane = -1;
   const void* last_sky_slot = nullptr;
   uint64_t last_sky_id = 0, rec_ids = 0;
+  // Lean tiles (rt_ctx_set_option(RT_OPT_LEAN_TILES), rt_bodies.h lean_body): the entries whose record carries
+  // the lean bit are rendered by the program's lean kernel ahead of the megakernel.  last_lean_*: the last row
+  // launch's record table where it took the lean kernel.
+  bool lean_tiles = true;
+  const void* last_lean_slot = nullptr;
+  uint64_t last_lean_id = 0;
   int tile_masks = 1;                   // rt_ctx_set_option(RT_OPT_TILE_MASKS): 0 never, 1 where they pay (OrderSlot::masks_pay), 2 always
   bool masks_ok = false;                // the uploaded scene has a mask scene in its blob (<= 32 objects)
   const void* d_mask_scene = nullptr;   // RtTileMaskScene in the blob
@@ -256,12 +265,18 @@ bool masks_usable(const rt_ctx* c);            // the uploaded scene has a mask 
 int mask_slot(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t n_tiles, rt_ctx::MaskSlot** out);
 // The dispatch records (RecSlot) of a launch of n_entries order entries (d_order of calibration order_id; null and
 // 0: the identity) whose mask table is ms's, gathered on st first if the masks or the order are new.
+// lean: with the lean bits (RT_OPT_LEAN_TILES), set by the gather and cleared again by the program's check kernel
+// where a tile fails it, both on st ahead of the table's event; the context holds that kernel (LaunchPlan::lean).
 int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const int32_t* d_order, uint64_t order_id,
-                   uint32_t n_entries, const RtTileRec** table, const void** rslot = nullptr);
+                   uint32_t n_entries, bool lean, const RtTileRec** table, const void** rslot = nullptr);
 void drop_records(rt_ctx* c);                  // every record table (upload, free)
 // How many of a record table's entries say sky (rslot as launch_records gave it, rec_id its RecSlot::rec_id);
 // -1: the table has been dropped since, -2: its gather has not completed yet.  Never waits.
 int64_t record_sky_entries(rt_ctx* c, const void* rslot, uint64_t rec_id, uint32_t* n_entries);
+int64_t record_lean_entries(rt_ctx* c, const void* rslot, uint64_t rec_id);   // the entries that say lean, likewise
+// The run of entries [*first, *end) that holds every lean entry of the table, once its check has completed (true;
+// *end == *first: no entry is lean); false until then.  Never waits.
+bool record_lean_range(const void* rslot, uint32_t* first, uint32_t* end);
 uint64_t record_id(const void* rslot);
 size_t put_mask_scene(const FlatScene& f, std::vector<uint8_t>& blob, bool* ok);   // appends the RtTileMaskScene
 int ensure_scratch(rt_ctx* c, size_t bytes);   // grow-only device scratch for host-pointer launches
@@ -289,6 +304,7 @@ void spec_prepare(rt_ctx* c, bool retry = false);   // describe and request c's 
 int spec_poll(rt_ctx* c);                           // load them if compiled: RT_OK, or RT_PENDING (spec.error on failure)
 int spec_wait(rt_ctx* c, double timeout_ms);        // block (< 0: no limit) then spec_poll
 void spec_drop(rt_ctx* c);                          // unload + release (no launch of c may be in flight)
+std::string spec_lean_note(const rt_ctx* c);        // why launches take no lean kernel although the program may hold them ("": no reason)
 // The loaded row kernel of `kind` for (f64, cal), or null (the generic kernels run).
 inline hipFunction_t spec_fn(const rt_ctx* c, int kind, bool f64, bool cal) {
   return c->spec.loaded ? c->spec.slots[kind][f64 ? 1 : 0][cal ? 1 : 0].function : nullptr;

@@ -292,6 +292,7 @@ int rt_ctx_upload(rt_ctx* c, const rt_scene* s) {
   c->sky_ok = rt::tilemask_sky_ok(f);
   c->mask_plane = rt::tilemask_plane(f);
   c->last_sky_slot = nullptr;
+  c->last_lean_slot = nullptr;
   d.n_objects = (int32_t)f.objects.size();
   d.n_lights = (int32_t)f.lights.size();
   d.n_leaves = (int32_t)f.leaves.size();
@@ -370,6 +371,11 @@ int rt_ctx_kernel_info(rt_ctx* c, char* buf, size_t cap) {
   // sky fill: the last launch's records could say sky; the counts come from a pinned word once the records'
   // gather has completed (no wait: "counts pending" until then, no counts once the table has been dropped).
   // (Ahead of "last launch": callers match the text from there to the end.)
+  const int64_t n_lean = c->last_lean_slot ? rt::record_lean_entries(c, c->last_lean_slot, c->last_lean_id) : -1;
+  s += !c->last_lean_slot ? "; lean tiles: off" + (c->lean_tiles ? rt::spec_lean_note(c) : std::string())
+       : n_lean >= 0      ? "; lean tiles: on (" + std::to_string(n_lean) + " entries)"
+       : n_lean == -2     ? "; lean tiles: on (count pending)"
+                          : "; lean tiles: on";
   uint32_t n_entries = 0;
   const int64_t n_sky = c->last_sky_slot ? rt::record_sky_entries(c, c->last_sky_slot, c->last_sky_id, &n_entries) : -1;
   if (n_sky >= 0)
@@ -454,6 +460,11 @@ int rt_ctx_set_option(rt_ctx* c, int32_t option, int32_t value) {
   if (option == RT_OPT_SKY_FILL) {
     if (value != 0 && value != 1) return fail(RT_ERR_INVALID, "RT_OPT_SKY_FILL value %d", value);
     c->sky_fill = value != 0;            // record tables are keyed by it: the next launch gathers its own
+    return RT_OK;
+  }
+  if (option == RT_OPT_LEAN_TILES) {
+    if (value != 0 && value != 1) return fail(RT_ERR_INVALID, "RT_OPT_LEAN_TILES value %d", value);
+    c->lean_tiles = value != 0;          // record tables are keyed by it: the next launch gathers its own
     return RT_OK;
   }
   if (option == RT_OPT_WAVEFRONT_PAIRS) {

@@ -287,6 +287,75 @@ __device__ __forceinline__ TileMask tile_mask_ones() {
   return m;
 }
 
+// The light of a hit (raytracer.rs:172-228) and its inside test (:230-235), each written ONCE, as statement
+// macros: trace() expands them in place and the lean kernel's functions (hit_lights, hit_inside below) expand the
+// same text, so the two cannot diverge.  They are macros and not functions that trace() calls because the same
+// statements behind an inlined call cost the 4K globes megakernel two spilled VGPRs; expanded
+// in place trace() compiles to the code it had.
+// RT_HIT_LIGHTS: over the names S, oi, p (the hit), FC, SHARE, OBB, and nrm, c, L, transp, refl, nlen, which it
+// sets.  SMASK: statements that may set `smask`, the tile-mask word of light k's shadow walk (all ones: none).
+// Evaluation order is free (every step is a pure function of the hit), so the shadow
+// rays of a group of lights are traced FIRST, while only the hit point is live, and the
+// normal / UV / material and the per-light Lambert terms are formed afterwards: far fewer
+// registers live across the traversals.  Light accumulation order is unchanged.
+// One light at a time: the unit vector towards the light is the shadow ray's direction
+// (:176-178) AND the Lambert term's `sdir` (:203-205), the same operations on the same
+// operands, so it is formed once and kept for the Lambert term.
+#define RT_HIT_LIGHTS(SMASK)                                                                         \
+  {                                                                                                  \
+    bool have_shading = false;                                                                       \
+    _Pragma("unroll 1") for (int k = 0; k < S.n_lights; ++k) {                                       \
+      RT_REC(lt, S, lights, LIGHTS, k);                                                              \
+      const V3 lv = sub(ld3(lt->p), p);                                                              \
+      double ll, ill;                                                                                \
+      len_inv(lv, &ll, &ill);                                                                        \
+      const V3 sdir = scale(lv, ill);                                    /* normalized(lv) */        \
+      double t;                                                          /* :176-197 */              \
+      uint32_t smask = 0xffffffffu;                                                                  \
+      SMASK                                                                                          \
+      t = shadow_transparency<SHARE, OBB>(S, p, sdir, ll, smask);                                    \
+      if (!have_shading) {                                                                           \
+        shade_inputs(S, oi, p, &nrm, &c, &transp, &refl, &nlen);                                     \
+        L = cmul<FC>(c, in_range<FC>(0.6, 0.6, 0.6));                      /* ambient (:172) */      \
+        have_shading = true;                                                                         \
+      }                                                                                              \
+      if (t == 0.0) continue;                                            /* :199-227 */              \
+      double ang = rt_acos(dot(sdir, nrm) / (len(sdir) * nlen));                                     \
+      if (ang >= PI_D / 2.0) ang = PI_D - ang;                                                       \
+      const double inten = (ang < (PI_D / 2.0) && ang >= 0.0) ? 1.0 - lambert_ratio(ang) : 0.0;      \
+      const Col lc = intensify<FC>(intensify<FC>(Col{lt->col[0], lt->col[1], lt->col[2]}, inten), t); \
+      L = cadd<FC>(L, cmul<FC>(c, lc));                                                              \
+    }                                                                                                \
+    if (!have_shading) {                                                                             \
+      shade_inputs(S, oi, p, &nrm, &c, &transp, &refl, &nlen);                                       \
+      L = cmul<FC>(c, in_range<FC>(0.6, 0.6, 0.6));                                                  \
+    }                                                                                                \
+  }
+// RT_HIT_INSIDE: sets `inside` from the ray direction rd and the hit's nrm, nlen.
+#define RT_HIT_INSIDE()                                                                              \
+  {                                                                                                  \
+    const V3 nd = scale(rd, -1.0);                                                                   \
+    const double d = dot(nd, nrm);                                                                   \
+    if (!(outside_certain(d, dot(nd, nd), nlen)))                                                    \
+      inside = inside_test(d / (len(nd) * nlen));                                                    \
+  }
+// The same as functions, for the lean kernel (rt_bodies.h lean_pixel): every shadow walk under the mask `smask_all`.
+template <bool FC, bool SHARE, bool OBB>
+RT_FN Col hit_lights(const DS& S, int oi, V3 p, uint32_t smask_all, V3* nrm_out, Col* c_out, double* transp_out,
+                     double* refl_out, double* nlen_out) {
+  V3 nrm = {0.0, 0.0, 0.0};
+  Col c = {0.0, 0.0, 0.0}, L = {0.0, 0.0, 0.0};
+  double transp = 0.0, refl = 0.0, nlen = 0.0;
+  RT_HIT_LIGHTS(smask = smask_all;)
+  *nrm_out = nrm; *c_out = c; *transp_out = transp; *refl_out = refl; *nlen_out = nlen;
+  return L;
+}
+__device__ __forceinline__ bool hit_inside(V3 rd, V3 nrm, double nlen) {
+  bool inside = false;
+  RT_HIT_INSIDE()
+  return inside;
+}
+
 // get_ray_color (raytracer.rs:132-287) for one primary ray, recursion unrolled onto a per-lane
 // frame stack.  REFR = the scene has a transparent object (refraction frames need more state).
 // KL > 0: frames 0..KL-1 of the stack are in LDS at lf[(f * 4 + c) * 64] (lf = this lane's slot);
@@ -428,47 +497,14 @@ RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, ld
     Col c = {0.0, 0.0, 0.0}, L = {0.0, 0.0, 0.0};
     double transp = 0.0, refl = 0.0, nlen = 0.0;
     if (oi >= 0) {
-      // Evaluation order is free (every step is a pure function of the hit), so the shadow
-      // rays of a group of lights are traced FIRST, while only the hit point is live, and the
-      // normal / UV / material and the per-light Lambert terms are formed afterwards: far fewer
-      // registers live across the traversals.  Light accumulation order is unchanged.
-      bool have_shading = false;
-      // One light at a time: the unit vector towards the light is the shadow ray's direction
-      // (:176-178) AND the Lambert term's `sdir` (:203-205), the same operations on the same
-      // operands, so it is formed once and kept for the Lambert term.
-#pragma unroll 1
-      for (int k = 0; k < S.n_lights; ++k) {
-        RT_REC(lt, S, lights, LIGHTS, k);
-        const V3 lv = sub(ld3(lt->p), p);
-        double ll, ill;
-        len_inv(lv, &ll, &ill);
-        const V3 sdir = scale(lv, ill);                                    // normalized(lv)
-        double t;                                                          // :176-197
-        uint32_t smask = 0xffffffffu;
+      // (k is the same in every lane, but the loop sits in the branch of the lanes that hit: the word is
+      // chosen by its first-lane copy, scalar selects)
+      RT_HIT_LIGHTS(
         if constexpr (MASKS)
           if (__builtin_amdgcn_readfirstlane((int)(plane_tile && iter == 0)) != 0 && k < 4) {
-            // (k is the same in every lane, but the loop sits in the branch of the lanes that hit: the word is
-            // chosen by its first-lane copy, scalar selects)
             const int ks = __builtin_amdgcn_readfirstlane(k);
             smask = ks == 0 ? tm.w[1] : ks == 1 ? tm.w[2] : ks == 2 ? tm.w[3] : tm.w[4];
-          }
-        t = shadow_transparency<SHARE, OBB>(S, p, sdir, ll, smask);
-        if (!have_shading) {
-          shade_inputs(S, oi, p, &nrm, &c, &transp, &refl, &nlen);
-          L = cmul<FC>(c, in_range<FC>(0.6, 0.6, 0.6));                      // ambient (:172)
-          have_shading = true;
-        }
-        if (t == 0.0) continue;                                            // :199-227
-        double ang = rt_acos(dot(sdir, nrm) / (len(sdir) * nlen));
-        if (ang >= PI_D / 2.0) ang = PI_D - ang;
-        const double inten = (ang < (PI_D / 2.0) && ang >= 0.0) ? 1.0 - lambert_ratio(ang) : 0.0;
-        const Col lc = intensify<FC>(intensify<FC>(Col{lt->col[0], lt->col[1], lt->col[2]}, inten), t);
-        L = cadd<FC>(L, cmul<FC>(c, lc));
-      }
-      if (!have_shading) {
-        shade_inputs(S, oi, p, &nrm, &c, &transp, &refl, &nlen);
-        L = cmul<FC>(c, in_range<FC>(0.6, 0.6, 0.6));
-      }
+          })
     }
     if (oi < 0) {
       C = {0.0, 0.0, 0.0};                                               // Color::BLACK (:152-160)
@@ -478,10 +514,7 @@ RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, ld
       // and square roots (the values it would give are never read).
       bool inside = false;
       if (depth < max_depth && (refl != 0.0 || (REFR && transp != 0.0))) {
-        const V3 nd = scale(rd, -1.0);
-        const double d = dot(nd, nrm);
-        if (!(outside_certain(d, dot(nd, nd), nlen)))
-          inside = inside_test(d / (len(nd) * nlen));
+        RT_HIT_INSIDE()
       }
       const V3 n2 = inside ? scale(nrm, -1.0) : nrm;
       const double r1 = inside ? 1.45 : 1.0, r2 = inside ? 1.0 : 1.45;

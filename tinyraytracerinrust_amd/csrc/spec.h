@@ -35,6 +35,8 @@ enum SpecKind {
   SPEC_VIEWS,         // a two-eye scene's view megakernel (its program holds nothing else)
   SPEC_POINTS,        // rt_render_points_f64's kernel
   SPEC_AA,            // rt_antialias' trace passes
+  SPEC_LEAN,          // the lean kernel of the megakernel's launches (RT_OPT_LEAN_TILES; rt_bodies.h lean_body)
+  SPEC_LEAN_CHECK,    // its check, run once per record table (k_masks.hip launch_records)
   SPEC_KINDS
 };
 // The known-good scratch bound a code object is held to (spec_compile.cpp spec_guard).
@@ -50,12 +52,13 @@ struct SpecKindRow {
   bool frames;          // declares the LDS frames (rows_lds_doubles of the mode and layout)
   bool masks;           // takes the mask operand, and RT_REC_PARAMS in a reflection-only program
   bool no_tile_masks;   // its program is prefixed with RT_TILE_MASKS 0
-  enum { WAVES_MODE, WAVES_PRIMARY, WAVES_DEFERRED } waves;   // where amdgpu_waves_per_eu comes from
+  enum { WAVES_MODE, WAVES_PRIMARY, WAVES_DEFERRED, WAVES_LEAN } waves;   // where amdgpu_waves_per_eu comes from
   bool variants;        // [f64][cal] instantiations (level 2: all four; level 1: the product's one)
-  enum { ONE_EYE, REFLECTION, CONTEXT_REFLECTION, TWO_EYES, SAMPLE } held;   // which programs hold it (spec_kernels)
+  enum { ONE_EYE, REFLECTION, CONTEXT_REFLECTION, TWO_EYES, SAMPLE, LEAN } held;   // which programs hold it (spec_kernels)
   SpecBound bound;      // SPEC_BOUND_ROWS: by the mode (ray trees: SPEC_BOUND_TREE)
   const char* generic;  // last_sample's words for the generic kernel (sample kinds)
   const char* specialised;
+  bool no_cal = false;  // variants: [f64] only, no calibrating form ("%d" = f64)
 };
 const SpecKindRow& spec_kind(int kind);
 inline bool spec_is_sample(int kind) { return spec_kind(kind).held == SpecKindRow::SAMPLE; }
@@ -69,13 +72,15 @@ struct SpecProgram {
   bool deferred = false;  // also holds the deferred kernels
   bool fits = false;      // small enough to specialise (RT_SPEC_MAX_OBJECTS / _LEAVES)
   int family = 0;         // > 0: the program of a registered scene family of that many members
+  bool lean = false;      // may hold the lean kernels: reflection-only, one eye, tilemask_lean_ok (and no family)
   int level = 1;          // RT_OPT_SPECIALIZE: 0 off, 1 the product launches, 2 every row launch
 };
 SpecProgram spec_describe(const FlatScene& f, int level);
 struct SpecKernel { int kind, f64, cal; };
 // The kernels of p's programs, in catalogue order: a scene's row programs as rt_scene_precompile, _spec_report
 // and _spec_program name them; a CONTEXT's row programs, which add the mask-free megakernel; the sample programs.
-enum SpecSet { SPEC_SET_SCENE, SPEC_SET_CONTEXT, SPEC_SET_SAMPLES };
+// The lean kernels are a set of their own (rt_scene_lean_report) that a context's row programs include.
+enum SpecSet { SPEC_SET_SCENE, SPEC_SET_CONTEXT, SPEC_SET_SAMPLES, SPEC_SET_LEAN };
 std::vector<SpecKernel> spec_kernels(const SpecProgram& p, SpecSet set);
 std::string spec_kernel_name(const SpecKernel& k);
 std::string spec_program_text(const SpecProgram& p, const SpecKernel& k);   // prefix + prelude + the one kernel
@@ -83,6 +88,7 @@ SpecBound spec_bound(const SpecProgram& p, int kind);
 bool same_structure_flat(const FlatScene& a, const FlatScene& b);   // a scene family's structure test
 int tilemask_plane(const FlatScene& f);        // k_masks.hip: the mask plane's object index, -1: none
 bool tilemask_sky_ok(const FlatScene& f);      // k_masks.hip: a tile whose prim word is 0 is sky (SKY_OK)
+bool tilemask_lean_ok(const FlatScene& f);     // k_masks.hip: a record may say lean (LEAN_OK)
 uint64_t fnv1a(const std::string& s);
 
 // ---- the compiler (spec_compile.cpp) ---------------------------------------------------------------

@@ -107,11 +107,27 @@ void spec_prepare(rt_ctx* c, bool retry) {
   if (S.samples_wanted) spec_samples_request(c, retry);
 }
 
+// The lean kernels (RT_OPT_LEAN_TILES) are requested with the row programs, behind them in the pool, but the row
+// programs do not wait for them: each loads when its compile has finished (launches run without lean tiles until
+// both are there, launch_plan.h has_lean), and one that fails only leaves its slot empty.
+static bool is_lean(const SpecKernel& k) { return spec_kind(k.kind).held == SpecKindRow::LEAN; }
+static void lean_poll(rt_ctx* c) {
+  for (const SpecKernel& k : spec_kernels(c->spec.prog, SPEC_SET_LEAN)) {
+    SpecSlot& s = slot_of(c, k);
+    if (s.job && job_finished(s.job.get())) (void)slot_load(s, k);
+  }
+}
+
 // The row programs load all or nothing: one failure drops them and says why.
 int spec_poll(rt_ctx* c) {
   rt_ctx::Spec& S = c->spec;
-  if (!S.pending) return RT_OK;
-  const std::vector<SpecKernel> ks = spec_kernels(S.prog, SPEC_SET_CONTEXT);
+  if (!S.pending) {
+    if (S.loaded) lean_poll(c);
+    return RT_OK;
+  }
+  std::vector<SpecKernel> ks;
+  for (const SpecKernel& k : spec_kernels(S.prog, SPEC_SET_CONTEXT))
+    if (!is_lean(k)) ks.push_back(k);
   for (const SpecKernel& k : ks)
     if (!job_finished(slot_of(c, k).job.get())) return RT_PENDING;
   for (const SpecKernel& k : ks) {
@@ -140,6 +156,7 @@ int spec_poll(rt_ctx* c) {
   S.res = slot_of(c, ks[0]).res;
   if (disk && S.note.empty()) S.note = " [disk cache]";
   S.ready_ms = now_ms() - S.t0;
+  lean_poll(c);
   // Orders built while the generic kernels ran may have chosen the deferred kernel for a tail-bound
   // launch (split entries); with the specialised megakernel loaded that choice no longer pays
   // (k_rows.hip): those geometries calibrate again.
@@ -148,9 +165,24 @@ int spec_poll(rt_ctx* c) {
   return RT_OK;
 }
 
+// (the lean kernels too, also when a launch has loaded the row programs already: a host that waits gets lean
+// tiles from its next frame on)
 int spec_wait(rt_ctx* c, double timeout_ms) {
-  if (c->spec.pending && !slots_wait(c, spec_kernels(c->spec.prog, SPEC_SET_CONTEXT), timeout_ms)) return RT_PENDING;
+  if ((c->spec.pending || c->spec.loaded) && !slots_wait(c, spec_kernels(c->spec.prog, SPEC_SET_CONTEXT), timeout_ms))
+    return RT_PENDING;
   return spec_poll(c);
+}
+
+// rt_ctx_kernel_info's words on the lean kernels of a loaded program that may hold them: "" where all is well
+std::string spec_lean_note(const rt_ctx* c) {
+  if (!c->spec.loaded) return "";
+  for (const SpecKernel& k : spec_kernels(c->spec.prog, SPEC_SET_LEAN)) {
+    const SpecSlot& s = c->spec.slots[k.kind][k.f64][k.cal];
+    if (s.function) continue;
+    if (s.job) return " (the lean kernels are compiling in the background)";
+    if (!s.error.empty()) return " (" + spec_kernel_name(k) + " failed: " + s.error + ")";
+  }
+  return "";
 }
 
 // ---- the sample programs: loaded, failed and reported per kernel -----------------------------------

@@ -164,6 +164,8 @@ std::string spec_source(const FlatScene& f, const SpecFamily* fam) {
   s += buf;
   // sky tiles (rt_device.h rows_entry): every object is boxed or the mask plane, so prim words can be 0
   s += std::string("constexpr bool SKY_OK = ") + (!fam && tilemask_sky_ok(f) ? "true" : "false") + ";\n";
+  // lean tiles (rt_bodies.h rows_entry, lean_body): a record may carry the lean bit, the megakernel returns on it
+  s += std::string("constexpr bool LEAN_OK = ") + (!fam && tilemask_lean_ok(f) ? "true" : "false") + ";\n";
   emit_table(s, "RtObject", "OBJECTS", f.objects, fam ? &fam->v_obj : nullptr);
   emit_table(s, "RtTrav", "TRAV", f.trav, fam ? &fam->v_trav : nullptr);
   emit_table(s, "RtTrav", "STRAV", f.strav, fam ? &fam->v_strav : nullptr);
@@ -211,6 +213,11 @@ std::string spec_frame_layout() {
 #define RT_SPEC_WAVES_PRIM 4
 #endif
 
+// The lean kernels (rt_bodies.h lean_body): one plane hit, its lights and a fold -- 8 waves' registers.
+#ifndef RT_SPEC_WAVES_LEAN
+#define RT_SPEC_WAVES_LEAN 8
+#endif
+
 // The catalogue: one row per SpecKind (spec.h SpecKindRow), the generic kernels' exact bodies.  The row kernels
 // share the generic kernels' parameters; the megakernel and the primary-ray kernel also take the launch
 // geometry's tile-mask table (null: all ones) -- and, in a masked program of a reflection-only scene
@@ -248,6 +255,15 @@ const SpecKindRow spec_kinds[SPEC_KINDS] = {
                    "double* __restrict__ col, int max_depth",
                    "", "aa_trace_body", "$M, $X, $L", "S, edges, req, n, size, col, max_depth, $S", true, false, true,
                    K::WAVES_MODE, false, K::SAMPLE, SPEC_BOUND_ROWS, "aa trace", "aa trace (specialised)"},
+    // the lean kernel takes the megakernel's operands (one argument list serves both launches), the check the
+    // launch geometry and the record table it edits
+    /* SPEC_LEAN */ {"rt_spec_lean_%d", "RtDevScene S, " ROW_PARAMS, "", "lean_body", "$F, $X",
+                     "S, y_first, band_rows, band_pitch, n_rows, max_depth, out, stride, rgb$R", false, true, false,
+                     K::WAVES_LEAN, true, K::LEAN, SPEC_BOUND_ROWS, nullptr, nullptr, true},
+    /* SPEC_LEAN_CHECK */ {"rt_spec_lean_check",
+                           "RtDevScene S, int y_first, int band_rows, int band_pitch, int n_rows, RtTileRec* __restrict__ recs",
+                           "", "lean_check_body", "$X", "S, y_first, band_rows, band_pitch, n_rows, recs", false, false,
+                           false, K::WAVES_LEAN, false, K::LEAN, SPEC_BOUND_ROWS, nullptr, nullptr},
 };
 
 // s with every $-placeholder of the catalogue replaced (vars: pairs of letter and text).
@@ -273,6 +289,7 @@ std::string spec_kernel(const SpecProgram& p, const SpecKernel& k) {
       {'D', tf(p.mode != RT_MODE_REFL)}, {'S', row.frames ? "(lds_f64*)s_frames" : "nullptr"}, {'R', recs ? " RT_REC_ARGS" : ""}};
   const std::string waves = row.waves == K::WAVES_DEFERRED  ? "RT_WAVES_PER_EU_DEFERRED"
                             : row.waves == K::WAVES_PRIMARY ? std::to_string(RT_SPEC_WAVES_PRIM)
+                            : row.waves == K::WAVES_LEAN    ? std::to_string(RT_SPEC_WAVES_LEAN)
                                                             : std::to_string(p.mode == RT_MODE_CHAIN ? RT_SPEC_WAVES_CHAIN : RT_SPEC_WAVES);
   std::string s = "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(" + waves + "))) void " +
                   spec_kernel_name(k) + "(" + row.params;
@@ -295,6 +312,7 @@ SpecProgram spec_flags(const FlatScene& f, int level) {
   p.fc = f.colour_fast != 0;
   p.two_eyes = f.cam_kind != RT_CAMERA_PERSPECTIVE;
   p.deferred = p.mode == RT_MODE_REFL && !p.two_eyes;
+  p.lean = p.mode == RT_MODE_REFL && !p.two_eyes && tilemask_lean_ok(f);
   return p;
 }
 
@@ -409,11 +427,13 @@ std::vector<SpecKernel> spec_kernels(const SpecProgram& p, SpecSet set) {
       case K::CONTEXT_REFLECTION: held = set == SPEC_SET_CONTEXT && !p.two_eyes && p.mode == RT_MODE_REFL && !p.family; break;
       case K::TWO_EYES: held = set != SPEC_SET_SAMPLES && p.two_eyes; break;
       case K::SAMPLE: held = set == SPEC_SET_SAMPLES && !p.two_eyes; break;
+      case K::LEAN: held = (set == SPEC_SET_CONTEXT || set == SPEC_SET_LEAN) && p.lean && !p.family; break;
     }
+    if (set == SPEC_SET_LEAN && row.held != K::LEAN) continue;
     if (!held) continue;
     const int n = row.variants && p.level >= 2 ? 2 : 1;
     for (int f64 = 0; f64 < n; ++f64)
-      for (int cal = 0; cal < n; ++cal) v.push_back({kind, f64, cal});
+      for (int cal = 0; cal < (row.no_cal ? 1 : n); ++cal) v.push_back({kind, f64, cal});
   }
   return v;
 }
@@ -441,7 +461,18 @@ extern "C" int rt_scene_precompile(const rt_scene* s, double* compile_ms) {
   if (!s) return fail(RT_ERR_INVALID, "null scene");
   Requested r;
   double ms = 0.0;
-  const int rc = scene_programs(s, SPEC_SET_SCENE, &r, &ms);
+  // the row programs and the lean kernels a context's row programs include, all requested before any is waited for
+  FlatScene f;
+  RT_TRY(flatten(*s, &f));
+  const SpecProgram p = spec_describe(f, 1);
+  int rc = RT_OK;
+  if (!p.fits) {
+    rc = not_specialised(f, false);
+  } else {
+    r.add(p, SPEC_SET_SCENE);
+    r.add(p, SPEC_SET_LEAN);
+    rc = r.wait(&ms);
+  }
   if (compile_ms) *compile_ms = ms;
   return rc;
 }
@@ -469,6 +500,16 @@ extern "C" int rt_scene_sample_report(const rt_scene* s, char* buf, size_t cap, 
   return copy_out(r.report(), buf, cap, len);
 }
 
+// rt_scene_lean_report (include/rt_abi.h): compile (or find) the scene's lean kernels (RT_OPT_LEAN_TILES), no device
+// needed, and describe them in rt_scene_spec_report's format; a scene whose programs hold none: no lines
+extern "C" int rt_scene_lean_report(const rt_scene* s, char* buf, size_t cap, size_t* len) {
+  if (!s || !len || (cap > 0 && !buf)) return fail(RT_ERR_INVALID, "null argument");
+  Requested r;
+  double ms = 0.0;
+  RT_TRY(scene_programs(s, SPEC_SET_LEAN, &r, &ms));
+  return copy_out(r.report(), buf, cap, len);
+}
+
 // rt_scene_spec_program (include/rt_abi.h): the prelude and every kernel rt_scene_precompile compiles
 // (at level 2: with the f64 and calibration instantiations; a scene too large to specialise has a text too)
 extern "C" int rt_scene_spec_program(const rt_scene* s, char* buf, size_t cap, size_t* len) {
@@ -479,6 +520,7 @@ extern "C" int rt_scene_spec_program(const rt_scene* s, char* buf, size_t cap, s
   if (!p.fits) spec_prelude(f, &p);
   std::string text = p.src;
   for (const SpecKernel& k : spec_kernels(p, SPEC_SET_SCENE)) text += spec_kernel(p, k);
+  for (const SpecKernel& k : spec_kernels(p, SPEC_SET_LEAN)) text += spec_kernel(p, k);   // (a context's, where held)
   return copy_out(text, buf, cap, len);
 }
 
@@ -534,6 +576,7 @@ extern "C" int rt_spec_family_register(const rt_scene* const* scenes, int32_t n,
     p.src = F->src = spec_source(F->base, F->members > 1 ? F.get() : nullptr);
     first[fi] = all.jobs.size();
     all.add(p, SPEC_SET_SCENE);
+    if (F->members == 1) all.add(p, SPEC_SET_LEAN);  // (a family program holds none)
     F->jobs.assign(all.jobs.begin() + first[fi], all.jobs.end());
   }
   // every class's programs, compiled by the pool in parallel; the families whose programs compiled and

@@ -215,6 +215,16 @@ class Scene:
         check(lib().rt_scene_sample_report(self.h, buf, n.value + 1, ctypes.byref(n)))
         return buf.value.decode()
 
+    def lean_report(self) -> str:
+        """rt_scene_lean_report: compile (or find) the scene's lean kernels (RT_OPT_LEAN_TILES: rt_spec_lean_0 and
+        rt_spec_lean_check) and describe them, one line per kernel in spec_report's format; "" for a scene whose
+        programs hold none."""
+        n = ctypes.c_size_t()
+        check(lib().rt_scene_lean_report(self.h, None, 0, ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(n.value + 1)
+        check(lib().rt_scene_lean_report(self.h, buf, n.value + 1, ctypes.byref(n)))
+        return buf.value.decode()
+
     @staticmethod
     def register_family(scenes) -> float:
         """rt_spec_family_register: one specialised program for scenes of the same structure (the
@@ -532,6 +542,11 @@ class Renderer:
         """rt_ctx_set_option(RT_OPT_SKY_FILL): waves of sky tiles (an empty ``prim`` word in the dispatch record)
         store BLACK and return (default on); off, the records mark no tile as sky.  Same pixels."""
         check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_SKY_FILL, 1 if on else 0))
+
+    def set_lean_tiles(self, on: bool) -> None:
+        """rt_ctx_set_option(RT_OPT_LEAN_TILES): the entries of a megakernel launch whose rays can meet the floor
+        alone are rendered by the program's lean kernel ahead of the megakernel (default on).  Same pixels."""
+        check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_LEAN_TILES, 1 if on else 0))
 
     def tile_masks(self, y_first: int = 0, band_rows: Optional[int] = None, band_pitch: Optional[int] = None,
                    n_bands: int = 1) -> np.ndarray:

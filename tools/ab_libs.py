@@ -5,7 +5,8 @@ ms per frame (one event pair around --frames launches) per library, median over 
 usage: python tools/ab_libs.py LIB [LIB ...] [--config sphere1080d0|globes1080d5|globes4k|spin1080|fractal1080] [--generic]
        [--masks=-1,1,0]   per library: RT_OPT_TILE_MASKS (-1: leave it, for libraries without the option)
        [--records=-1,1,0] per library: RT_OPT_TILE_RECORDS (-1: leave it)
-       [--sky=-1,1,0]     per library: RT_OPT_SKY_FILL (-1: leave it)"""
+       [--sky=-1,1,0]     per library: RT_OPT_SKY_FILL (-1: leave it)
+       [--lean=-1,1,0]    per library: RT_OPT_LEAN_TILES (-1: leave it)"""
 import argparse
 import ctypes
 import os
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--masks", default="", help="per library (in order): RT_OPT_TILE_MASKS, -1 = leave the default")
     ap.add_argument("--records", default="", help="per library (in order): RT_OPT_TILE_RECORDS, -1 = leave the default")
     ap.add_argument("--sky", default="", help="per library (in order): RT_OPT_SKY_FILL, -1 = leave the default")
+    ap.add_argument("--lean", default="", help="per library (in order): RT_OPT_LEAN_TILES, -1 = leave the default")
     a = ap.parse_args()
     import torch
     scene, W, H, depth = CONFIGS[a.config]
@@ -43,7 +45,8 @@ def main():
     masks = [int(v) for v in a.masks.split(",")] if a.masks else [-1] * len(a.libs)
     records = [int(v) for v in a.records.split(",")] if a.records else [-1] * len(a.libs)
     sky = [int(v) for v in a.sky.split(",")] if a.sky else [-1] * len(a.libs)
-    for path, level, mask, rec, sk in zip(a.libs, levels, masks, records, sky):
+    lean = [int(v) for v in a.lean.split(",")] if a.lean else [-1] * len(a.libs)
+    for path, level, mask, rec, sk, le in zip(a.libs, levels, masks, records, sky, lean):
         L = ctypes.CDLL(os.path.abspath(path), mode=os.RTLD_LOCAL)
         L.rt_ctx_spec_wait.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         sc, cx = ctypes.c_void_p(), ctypes.c_void_p()
@@ -56,6 +59,8 @@ def main():
             assert L.rt_ctx_set_option(cx, 10, rec) == 0              # RT_OPT_TILE_RECORDS
         if sk >= 0:
             assert L.rt_ctx_set_option(cx, 11, sk) == 0               # RT_OPT_SKY_FILL
+        if le >= 0:
+            assert L.rt_ctx_set_option(cx, 12, le) == 0               # RT_OPT_LEAN_TILES
         assert L.rt_ctx_upload(cx, sc) == 0
         assert L.rt_ctx_spec_wait(cx, -1) == 0
         assert L.rt_ctx_set_option(cx, 1, 0) == 0                  # RT_OPT_TIMING off, as bench.py
@@ -96,10 +101,10 @@ def main():
         if not a.no_check and not torch.equal(outs[i], outs[0]):
             raise SystemExit(f"{a.libs[i]}: frame differs from {a.libs[0]}'s")
     print(f"{a.config} ({'generic' if a.generic else 'specialised'}), {n} frames per measurement, ms per frame, median of {a.rounds}:")
-    for path, level, mask, rec, sk, v in zip(a.libs, levels, masks, records, sky, res):
+    for path, level, mask, rec, sk, le, v in zip(a.libs, levels, masks, records, sky, lean, res):
         w = sorted(v)
         print(f"  {w[len(w) // 2]:.4f}  ({' '.join(f'{x:.4f}' for x in v)})  {path} (RT_OPT_SPECIALIZE {level}"
-              f"{'' if mask < 0 else f', RT_OPT_TILE_MASKS {mask}'}{'' if rec < 0 else f', RT_OPT_TILE_RECORDS {rec}'}{'' if sk < 0 else f', RT_OPT_SKY_FILL {sk}'})", flush=True)
+              f"{'' if mask < 0 else f', RT_OPT_TILE_MASKS {mask}'}{'' if rec < 0 else f', RT_OPT_TILE_RECORDS {rec}'}{'' if sk < 0 else f', RT_OPT_SKY_FILL {sk}'}{'' if le < 0 else f', RT_OPT_LEAN_TILES {le}'})", flush=True)
 
 
 if __name__ == "__main__":
