@@ -289,6 +289,35 @@ int rt_antialias_row_bands(rt_ctx* ctx, const uint8_t* src_rgba8, size_t src_str
  * threshold: RT_ERR_INVALID.  The predicate reads no camera, so two-eye scenes are served too. */
 int rt_antialias_edges(rt_ctx* ctx, const uint8_t* src_rgba8, size_t src_stride, double threshold,
                        uint8_t* overlay_rgba8, size_t overlay_stride, uint32_t* n_edges, void* stream);
+/* A render's ray counts, by the reference's own definitions -- ALGORITHMIC counts of the calls the reference
+ * makes, not what the culling render kernels execute: primary = get_pixel's camera rays (raytracer.rs:359-363:
+ * one per pixel, two per pixel of an anaglyph scene, camera.rs:186-193); reflect / refract = get_ray_color calls
+ * with RayType::ReflectionRay / TransmissionRay (raytracer.rs:274, :252); shadow = the lights of the scene for
+ * every ray of any type that hits an object (the loop over every light of every shaded hit, :175, whatever the
+ * depth).  The CPU oracle's counting build reports the same four. */
+typedef struct rt_ray_counts { uint64_t primary, shadow, reflect, refract; } rt_ray_counts;
+/* Counts the rays of the rows of a band layout of the uploaded scene (y_first, band_rows, band_pitch, n_bands as
+ * rt_render_row_bands; geometry and errors as rt_antialias_row_bands: band_rows == 0 or n_bands == 0: RT_OK,
+ * nothing written, *totals zeroed; band_pitch < band_rows with n_bands > 1, or y_first >= H: RT_ERR_INVALID;
+ * max_depth > 16: RT_ERR_UNSUPPORTED, < 0: the scene's).  One kernel walks every owned pixel's ray tree
+ * (get_ray_color, raytracer.rs:132-287) and stores no colour.  Three outputs, any of them NULL but not all:
+ *   totals        host: the launch's four sums; filling it synchronises the host with `stream`;
+ *   row_counts    device or host: 4 uint64 per PACKED row (band b row j at row b*band_rows + j, as
+ *                 rt_render_row_bands packs them): primary, shadow, reflect, refract;
+ *   pixel_counts  device or host: 4 uint32 per pixel in the same order, rows of pixel_stride_bytes >= 16 * W,
+ *                 packed likewise (device rows 16-byte aligned).
+ * Rows at or past H are not written.  Every figure is a sum of integers: exact, the same in any order, and over
+ * any partition of the frame into bands the totals sum to the frame's.  With device outputs and totals == NULL
+ * the call is asynchronous on `stream`.  Two-eye scenes are served: every pixel follows the scene's camera
+ * (stereoscopic: x >= W / 2 is the left eye's x - W / 2, camera.rs:124-131).  The call changes nothing about
+ * later renders (no tile order, no option, rt_ctx_kernel_info's last row launch); rt_ctx_last_kernel_ms then
+ * reports the counting kernel. */
+int rt_count_rays_row_bands(rt_ctx* ctx, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
+                            int32_t max_depth, rt_ray_counts* totals, uint64_t* row_counts,
+                            uint32_t* pixel_counts, size_t pixel_stride_bytes, void* stream);
+/* The same for rows [y0, y1) (y0 > y1 or y1 > H: RT_ERR_INVALID; y0 == y1: RT_OK, *totals zeroed). */
+int rt_count_rays(rt_ctx* ctx, uint32_t y0, uint32_t y1, int32_t max_depth, rt_ray_counts* totals,
+                  uint64_t* row_counts, uint32_t* pixel_counts, size_t pixel_stride_bytes, void* stream);
 /* Milliseconds of the last render launch on this context (HIP events recorded on the launch's
  * stream around the kernel; RT_OPT_TIMING 0 turns them off and this call then fails). */
 int rt_ctx_last_kernel_ms(rt_ctx* ctx, float* ms);

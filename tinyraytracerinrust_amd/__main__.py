@@ -4,6 +4,7 @@
                                           [--depth D] [--gpus N] [-o out.png]
                                           [--camera {perspective,stereoscopic,anaglyph} --eye-distance D]
                                           [--antialias [--aa-threshold T] [--aa-level L]]
+                                          [--count-rays] [--ray-map map.png]
 
 Replaces the reference's entry point and its GUI load path for this purpose: ``main()`` only
 starts the GTK application (src/main.rs:7-9), which builds a RayTracer per frame with
@@ -55,8 +56,19 @@ def _parse(argv):
                    help="mean |dRGBA| above which a cell subdivides (the GUI's ANTIALIAS_THRESHOLD, debug_window.rs:26)")
     r.add_argument("--aa-level", type=int, default=3,
                    help="subdivision levels, 0..4 (the GUI's ANTIALIAS_LEVEL, debug_window.rs:27)")
+    r.add_argument("--count-rays", action="store_true",
+                   help="count the frame's rays on the GPU by the reference's definitions (its algorithmic counts: "
+                        "primary, shadow, reflect, refract; rt_count_rays) and report them in the JSON line; with "
+                        "--gpus N every rank counts the bands it rendered")
+    r.add_argument("--ray-map", default=None, metavar="PATH",
+                   help="write the rays per pixel as a grey PNG, floor(255 * n / max n); implies --count-rays; "
+                        "not with --gpus > 1 (no rank holds the whole map)")
     r.add_argument("-o", "--output", default="out.png")
     a = ap.parse_args(argv)
+    if a.ray_map is not None:
+        if a.gpus > 1:
+            ap.error("--ray-map is not built for --gpus > 1 (no rank holds the whole map)")
+        a.count_rays = True
     if a.camera != "perspective" and a.eye_distance is None:
         ap.error(f"--camera {a.camera} needs --eye-distance (the reference constructs neither camera: no default)")
     if a.antialias and a.camera != "perspective":
@@ -161,6 +173,25 @@ def render(a) -> dict:
             frame, aa_rays = D.antialias_frame_distributed(antialias_bands, frame.contiguous(), H, W, dev, a.layout, band)
         torch.cuda.synchronize(dev)
         times["antialias_ms"] = (time.perf_counter() - t0) * 1e3
+    rays = None
+    if a.count_rays:
+        # the reference's algorithmic counts of the rows this rank rendered; one all-reduce sums the ranks'
+        t0 = time.perf_counter()
+        names = ("primary", "shadow", "reflect", "refract")
+        if world == 1:
+            res = r.count_rays(0, H, max_depth=a.depth, pixels=a.ray_map is not None)
+            counts = [res[k] for k in names]
+        else:
+            res = r.count_rays_row_bands(y_first, band_rows, pitch, n_bands, max_depth=a.depth) if n_bands else {}
+            sums = torch.tensor([res.get(k, 0) for k in names], dtype=torch.int64, device=dev)
+            dist.all_reduce(sums)
+            counts = [int(v) for v in sums.tolist()]
+        rays = dict(zip(names, counts), total=sum(counts))
+        times["count_ms"] = (time.perf_counter() - t0) * 1e3
+        if a.ray_map is not None:
+            n = res["pixels"].sum(axis=-1, dtype=np.uint64)
+            grey = (n * np.uint64(255) // max(n.max(), np.uint64(1))).astype(np.uint8)     # all zero: black
+            write_png(a.ray_map, np.ascontiguousarray(np.repeat(grey[..., None], 4, axis=-1)), channels=3)
     if rank == 0:
         t0 = time.perf_counter()
         host = frame.cpu().numpy()
@@ -171,7 +202,8 @@ def render(a) -> dict:
     if world > 1:
         dist.destroy_process_group()
     return {"output": a.output, "width": W, "height": H, "time": a.t, "gpus": world,
-            **{k: round(v, 3) for k, v in times.items()}, **({"aa_rays": aa_rays} if a.antialias else {})}
+            **{k: round(v, 3) for k, v in times.items()}, **({"aa_rays": aa_rays} if a.antialias else {}),
+            **({"rays": rays, "rays_per_pixel": round(rays["total"] / (W * H), 3)} if rays is not None else {})}
 
 
 def main(argv=None) -> int:

@@ -57,6 +57,11 @@ class rt_material(ctypes.Structure):
                 ("reflectivity", ctypes.c_double), ("transparency", ctypes.c_double)]
 
 
+class rt_ray_counts(ctypes.Structure):
+    _fields_ = [("primary", ctypes.c_uint64), ("shadow", ctypes.c_uint64), ("reflect", ctypes.c_uint64),
+                ("refract", ctypes.c_uint64)]
+
+
 _P = ctypes.c_void_p
 _D3 = ctypes.POINTER(ctypes.c_double)
 _XF = ctypes.POINTER(rt_transformation)
@@ -136,6 +141,9 @@ SIGNATURES = {
                                     ctypes.POINTER(ctypes.c_uint64), _P]),
     "rt_antialias_edges": (_I, [_P, _P, ctypes.c_size_t, ctypes.c_double, _P, ctypes.c_size_t,
                                 ctypes.POINTER(_U32), _P]),
+    "rt_count_rays_row_bands": (_I, [_P, _U32, _U32, _U32, _U32, ctypes.c_int32, ctypes.POINTER(rt_ray_counts), _P, _P,
+                                     ctypes.c_size_t, _P]),
+    "rt_count_rays": (_I, [_P, _U32, _U32, ctypes.c_int32, ctypes.POINTER(rt_ray_counts), _P, _P, ctypes.c_size_t, _P]),
     "rt_ctx_last_kernel_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
     "rt_ctx_synchronize": (_I, [_P]),
     "rt_ctx_set_option": (_I, [_P, ctypes.c_int32, ctypes.c_int32]),

@@ -465,6 +465,78 @@ class Renderer:
                                        ctypes.byref(n), ctypes.c_void_p(st)))
         return res, n.value
 
+    def _count(self, fn, geometry, n: int, max_depth, rows, pixels, out_rows, out_pixels, stream, totals) -> dict:
+        """The shared half of count_rays / count_rays_row_bands: ``n`` packed rows, ``geometry`` the call's
+        leading arguments."""
+        on_device = any(a is not None and not isinstance(a, np.ndarray) for a in (out_rows, out_pixels))
+        st = 0
+        if on_device:
+            import torch
+            st = (stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))).cuda_stream
+        elif stream is not None:
+            st = stream.cuda_stream
+        if out_rows is None and rows:
+            out_rows = np.zeros((n, 4), np.uint64)
+        if out_pixels is None and pixels:
+            out_pixels = np.zeros((n, self.width, 4), np.uint32)
+        if not totals and out_rows is None and out_pixels is None:
+            raise ValueError("nothing to count into: totals, rows and pixels are all off")
+
+        def address(a, shape, dtype, what):
+            if a is None:
+                return None, 0
+            if a.shape[0] < n or tuple(a.shape[1:]) != shape:
+                raise ValueError(f"{what} {tuple(a.shape)} holds fewer than {n} rows of {shape}")
+            # (torch's signed types of the same width serve as well: the counts are far below their sign bit)
+            signed = dtype[1:]                # "uint64" -> "int64"
+            _check_rows(a, signed if str(a.dtype).split(".")[-1] == signed else dtype, what)
+            if a.shape[0] == 0:
+                return None, 0
+            if isinstance(a, np.ndarray):
+                return a.ctypes.data, a.strides[0]
+            return a.data_ptr(), a.stride(0) * a.element_size()
+
+        rp, rs = address(out_rows, (4,), "uint64", "row counts")
+        if out_rows is not None and rs not in (0, 32):
+            raise ValueError("the row counts must be contiguous")
+        pp, ps = address(out_pixels, (self.width, 4), "uint32", "pixel counts")
+        t = _lib.rt_ray_counts()
+        res = {}
+        if totals or rp or pp:                # (no row at all: nothing to pass, the counts are zero)
+            check(fn(self.h, *geometry, int(max_depth), ctypes.byref(t) if totals else None, ctypes.c_void_p(rp),
+                     ctypes.c_void_p(pp), ps, ctypes.c_void_p(st)))
+        if totals:
+            res = {"primary": t.primary, "shadow": t.shadow, "reflect": t.reflect, "refract": t.refract,
+                   "total": t.primary + t.shadow + t.reflect + t.refract}
+        if out_rows is not None:
+            res["rows"] = out_rows
+        if out_pixels is not None:
+            res["pixels"] = out_pixels
+        return res
+
+    def count_rays(self, y0: int = 0, y1: Optional[int] = None, max_depth: int = -1, rows: bool = False,
+                   pixels: bool = False, out_rows=None, out_pixels=None, stream=None, totals: bool = True) -> dict:
+        """rt_count_rays: the ray counts of rows [y0, y1) (default: the whole frame) of the uploaded scene, by
+        the reference's definitions -- its ALGORITHMIC counts, not what the culling render kernels execute:
+        ``primary`` camera rays (one per pixel; two on an anaglyph scene), ``reflect`` / ``refract``
+        get_ray_color calls of those ray types, ``shadow`` = lights x rays that hit an object -- and their sum
+        ``total``.  With ``rows`` also ``"rows"``: (n, 4) uint64 per-row sums in that order; with ``pixels``
+        ``"pixels"``: (n, W, 4) uint32.  Both are numpy arrays, or the torch device tensors (or numpy arrays)
+        passed as ``out_rows`` / ``out_pixels``; with device tensors and ``totals=False`` the call is
+        asynchronous on ``stream`` (torch's current stream) and the dict holds no sums."""
+        y1 = self.height if y1 is None else y1
+        return self._count(lib().rt_count_rays, (int(y0), int(y1)), max(int(y1) - int(y0), 0), max_depth, rows, pixels,
+                           out_rows, out_pixels, stream, totals)
+
+    def count_rays_row_bands(self, y_first: int, band_rows: int, band_pitch: int, n_bands: int, max_depth: int = -1,
+                             rows: bool = False, pixels: bool = False, out_rows=None, out_pixels=None, stream=None,
+                             totals: bool = True) -> dict:
+        """rt_count_rays_row_bands: count_rays for the rows of a band layout (the geometry of render_row_bands).
+        The arrays hold the rows PACKED, band b row j at row b*band_rows + j of n_bands*band_rows rows; rows
+        past the frame's height are not written (arrays made here hold zeros there)."""
+        return self._count(lib().rt_count_rays_row_bands, (int(y_first), int(band_rows), int(band_pitch), int(n_bands)),
+                           int(band_rows) * int(n_bands), max_depth, rows, pixels, out_rows, out_pixels, stream, totals)
+
     def record_rays(self, x: float, y: float, max_depth: int = -1, cap: int = 1 << 17):
         """rt_record_rays: (records as a RAY_RECORD_DTYPE array in callback order, pixel colour)."""
         buf = np.zeros(cap, RAY_RECORD_DTYPE)
@@ -762,6 +834,11 @@ class RayTracer:
     def render_frame(self) -> np.ndarray:
         """The whole frame as RGBA8 (H, W, 4), quantised as easy_pixbuf.rs:46-53."""
         return self.renderer.render_rows_host(0, self.height)
+
+    def count_rays(self, rows: bool = False, pixels: bool = False) -> dict:
+        """The whole frame's ray counts at this tracer's max_depth (Renderer.count_rays): the reference's
+        algorithmic counts -- primary, shadow, reflect, refract and their total."""
+        return self.renderer.count_rays(0, self.height, self.max_depth, rows=rows, pixels=pixels)
 
     def render_orthogonal_view_line(self, y: int, ortho_axes: "OrthoAxes") -> np.ndarray:
         """DebugWindow::render_orthogonal_view_line (debug_window.rs:166-227): (W, 4) f64 colours."""
