@@ -128,7 +128,8 @@ int rt_scene_set_max_depth(rt_scene* scene, int32_t max_depth);                 
  * and the reference's GUI constructs neither).  RT_ERR_INVALID: an unknown kind, a non-finite eye distance,
  * stereoscopic on a scene less than 2 pixels wide.
  * Every get_pixel path follows the kind: rt_render_rows / _f64 / _row_bands / _row_bands_rgb8,
- * rt_render_points_f64, rt_trace_pixel_f64.  rt_render_ortho does not use the camera.  Out of scope for
+ * rt_render_points_f64, rt_trace_pixel_f64, rt_count_rays; rt_first_hits and its forms serve stereoscopic scenes
+ * and refuse anaglyph ones.  rt_render_ortho does not use the camera.  Out of scope for
  * two-eye scenes (RT_ERR_UNSUPPORTED): rt_antialias, rt_antialias_row_bands, rt_record_rays, rt_ctx_tile_masks, rt_scene_tile_masks. */
 typedef enum rt_camera_kind { RT_CAMERA_PERSPECTIVE = 0, RT_CAMERA_STEREOSCOPIC = 1, RT_CAMERA_ANAGLYPH = 2 } rt_camera_kind;
 int rt_scene_set_camera_kind(rt_scene* scene, int32_t kind, double eye_distance);
@@ -318,6 +319,47 @@ int rt_count_rays_row_bands(rt_ctx* ctx, uint32_t y_first, uint32_t band_rows, u
 /* The same for rows [y0, y1) (y0 > y1 or y1 > H: RT_ERR_INVALID; y0 == y1: RT_OK, *totals zeroed). */
 int rt_count_rays(rt_ctx* ctx, uint32_t y0, uint32_t y1, int32_t max_depth, rt_ray_counts* totals,
                   uint64_t* row_counts, uint32_t* pixel_counts, size_t pixel_stride_bytes, void* stream);
+/* First-hit maps: what a host asks about a frame BEFORE any shading -- which object is under each pixel, how far
+ * away, what its normal is there and which lights it can see (picking, depth / id / normal passes, shadow
+ * overlays).  One plane per answer, any of them NULL but not all; each a device or a host pointer of its own, rows
+ * of its stride in bytes:
+ *   object    int32: the draw index of the nearest hit of the pixel's camera ray (the first object with the
+ *             smallest distance d > EPS, raytracer.rs:141-150), -1 on a miss;
+ *   distance  double: that distance, INFINITY on a miss;
+ *   shadow    uint32: bit k set when light k's shadow ray from the hit point is occluded -- the product of the
+ *             transparencies of the hits between point and light is != 1.0 (raytracer.rs:176-197); 0 on a miss;
+ *             scenes of more than 32 lights: RT_ERR_UNSUPPORTED;
+ *   normal    3 doubles: the shape's raw get_normal at the hit point, NOT normalised, as the ray debugger
+ *             records it (ray_debugger.rs:113-119, rt_ray_record::normal); zeros on a miss.
+ * The hit has depth 0, so no max_depth is taken. */
+typedef struct rt_hit_planes {          /* any plane may be NULL, not all; strides in bytes */
+  int32_t*  object;   size_t object_stride;    /* draw index of the nearest hit, -1 = miss; rows >= 4*W  */
+  double*   distance; size_t distance_stride;  /* hit distance, INFINITY on a miss;        rows >= 8*W  */
+  uint32_t* shadow;   size_t shadow_stride;    /* bit k: light k's shadow ray is occluded; rows >= 4*W  */
+  double*   normal;   size_t normal_stride;    /* 3 doubles: the shape's raw get_normal;   rows >= 24*W */
+} rt_hit_planes;
+/* The first hits of rows [y0, y1) (y0 > y1 or y1 > H: RT_ERR_INVALID; y0 == y1: RT_OK, nothing written).  One
+ * kernel runs every pixel's nearest-hit walk and, only where the plane is asked for, its shadow walks and its
+ * normal; nothing is shaded.  A stride below its row: RT_ERR_INVALID, nothing written (device rows aligned to
+ * their element).  A host plane is staged in the context's scratch and copied back, and the call is then
+ * synchronous; with device planes only it is asynchronous on `stream`.  Stereoscopic scenes are served: every
+ * pixel follows the scene's camera (x >= W / 2 is the left eye's x - W / 2, camera.rs:124-131).  Anaglyph scenes:
+ * RT_ERR_UNSUPPORTED -- a pixel there has TWO first hits, one per eye (camera.rs:186-195), and a plane holds one.
+ * The call changes nothing about later renders (no tile order, no option, rt_ctx_kernel_info's last row launch);
+ * rt_ctx_last_kernel_ms then reports this kernel. */
+int rt_first_hits(rt_ctx* ctx, uint32_t y0, uint32_t y1, const rt_hit_planes* out, void* stream);
+/* The same for the rows of a band layout (y_first, band_rows, band_pitch, n_bands as rt_render_row_bands; geometry
+ * and errors as rt_count_rays_row_bands: band_rows == 0 or n_bands == 0: RT_OK, nothing written; band_pitch <
+ * band_rows with n_bands > 1, or y_first >= H: RT_ERR_INVALID).  Every plane holds the rows PACKED, band b row j
+ * at row b*band_rows + j; rows at or past H are not written. */
+int rt_first_hits_row_bands(rt_ctx* ctx, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch,
+                            uint32_t n_bands, const rt_hit_planes* out, void* stream);
+/* The same at n arbitrary sample positions (xy = n pairs of doubles, as rt_render_points_f64: the camera ray of
+ * get_pixel(x, y), fractional positions allowed): object[n], distance[n], shadow[n], normal[3n], contiguous; any
+ * of them NULL, not all; every pointer device or host (a host output makes the call synchronous).  A click in a
+ * host's frame is one such sample. */
+int rt_first_hits_points(rt_ctx* ctx, const double* xy, size_t n, int32_t* object, double* distance,
+                         uint32_t* shadow, double* normal, void* stream);   /* contiguous; any NULL, not all */
 /* Milliseconds of the last render launch on this context (HIP events recorded on the launch's
  * stream around the kernel; RT_OPT_TIMING 0 turns them off and this call then fails). */
 int rt_ctx_last_kernel_ms(rt_ctx* ctx, float* ms);

@@ -5,6 +5,8 @@
                                           [--camera {perspective,stereoscopic,anaglyph} --eye-distance D]
                                           [--antialias [--aa-threshold T] [--aa-level L]]
                                           [--count-rays] [--ray-map map.png]
+                                          [--object-map o.png] [--depth-map d.png] [--normal-map n.png]
+                                          [--shadow-map s.png]
 
 Replaces the reference's entry point and its GUI load path for this purpose: ``main()`` only
 starts the GTK application (src/main.rs:7-9), which builds a RayTracer per frame with
@@ -28,6 +30,9 @@ import socket
 import subprocess
 import sys
 import time
+
+
+HIT_MAP_FLAGS = ("--object-map", "--depth-map", "--normal-map", "--shadow-map")
 
 
 def _parse(argv):
@@ -63,8 +68,27 @@ def _parse(argv):
     r.add_argument("--ray-map", default=None, metavar="PATH",
                    help="write the rays per pixel as a grey PNG, floor(255 * n / max n); implies --count-rays; "
                         "not with --gpus > 1 (no rank holds the whole map)")
+    r.add_argument("--object-map", default=None, metavar="PATH",
+                   help="write the object under each pixel as a grey PNG (rt_first_hits): a miss 0, object o "
+                        "1 + o scaled to 1..255 over the scene's object count; one GPU, not with --camera anaglyph")
+    r.add_argument("--depth-map", default=None, metavar="PATH",
+                   help="write the first hit's distance as a grey PNG: the nearest white, the farthest dark grey, "
+                        "misses black; one GPU, not with --camera anaglyph")
+    r.add_argument("--normal-map", default=None, metavar="PATH",
+                   help="write the first hit's normal as an RGB PNG, normalised * 0.5 + 0.5, misses black; one GPU, "
+                        "not with --camera anaglyph")
+    r.add_argument("--shadow-map", default=None, metavar="PATH",
+                   help="write the share of the scene's lights each first hit can see as a grey PNG, misses black; "
+                        "one GPU, not with --camera anaglyph")
     r.add_argument("-o", "--output", default="out.png")
     a = ap.parse_args(argv)
+    for flag in HIT_MAP_FLAGS:
+        if getattr(a, flag[2:].replace("-", "_")) is None:
+            continue
+        if a.gpus > 1:
+            ap.error(f"{flag} is not built for --gpus > 1 (no rank holds the whole map)")
+        if a.camera == "anaglyph":
+            ap.error(f"{flag} is not built for --camera anaglyph (a pixel there has two first hits, one per eye)")
     if a.ray_map is not None:
         if a.gpus > 1:
             ap.error("--ray-map is not built for --gpus > 1 (no rank holds the whole map)")
@@ -102,6 +126,46 @@ def _self_launch(argv, gpus: int) -> int:
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     return subprocess.call(cmd, env=env)
+
+
+def hit_maps(a, planes, n_objects: int, n_lights: int):
+    """The first-hit maps the command line asked for, as (path, uint8 image) pairs from rt_first_hits' planes
+    (host arrays): grey (H, W) images, the normal map RGBA (H, W, 4).  Misses are black in every map."""
+    import numpy as np
+    obj = planes["object"]
+    hit = obj >= 0
+    if a.object_map is not None:
+        # object o -> (1 + o) * 255 / N, never below 1: 1..255 over the scene's N objects, a miss 0
+        grey = np.maximum((obj.astype(np.int64) + 1) * 255 // max(n_objects, 1), 1)
+        yield a.object_map, np.where(hit, grey, 0).astype(np.uint8)
+    if a.depth_map is not None:
+        # the nearest finite distance white (255), the farthest dark grey (64), linear in between
+        d = planes["distance"]
+        fin = hit & np.isfinite(d)
+        grey = np.zeros(d.shape, np.uint8)
+        if fin.any():
+            lo, hi = d[fin].min(), d[fin].max()
+            share = (d[fin] - lo) / (hi - lo) if hi > lo else np.zeros(int(fin.sum()))
+            grey[fin] = np.floor(255.0 - share * (255.0 - 64.0)).astype(np.uint8)
+        yield a.depth_map, grey
+    if a.normal_map is not None:
+        n = planes["normal"]
+        length = np.sqrt((n * n).sum(axis=-1, keepdims=True))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            unit = np.where(np.isfinite(length) & (length > 0.0), n / length, 0.0)
+        rgb = np.floor(np.clip(unit * 0.5 + 0.5, 0.0, 1.0) * 255.0).astype(np.uint8)
+        img = np.zeros(obj.shape + (4,), np.uint8)
+        img[..., :3] = np.where(hit[..., None], rgb, 0)
+        img[..., 3] = 255
+        yield a.normal_map, img
+    if a.shadow_map is not None:
+        # the share of the scene's lights the hit can see: lights - occluded bits, over lights
+        sh = planes["shadow"].astype(np.uint64)
+        occluded = np.zeros(sh.shape, np.int64)
+        for k in range(min(n_lights, 32)):
+            occluded += ((sh >> np.uint64(k)) & np.uint64(1)).astype(np.int64)
+        grey = (n_lights - occluded) * 255 // n_lights if n_lights > 0 else np.full(sh.shape, 255, np.int64)
+        yield a.shadow_map, np.where(hit, grey, 0).astype(np.uint8)
 
 
 def render(a) -> dict:
@@ -192,6 +256,18 @@ def render(a) -> dict:
             n = res["pixels"].sum(axis=-1, dtype=np.uint64)
             grey = (n * np.uint64(255) // max(n.max(), np.uint64(1))).astype(np.uint8)     # all zero: black
             write_png(a.ray_map, np.ascontiguousarray(np.repeat(grey[..., None], 4, axis=-1)), channels=3)
+    hits = None
+    if any(getattr(a, flag[2:].replace("-", "_")) is not None for flag in HIT_MAP_FLAGS):
+        # first-hit maps (one GPU: the parser refuses the others): one launch, only the planes the maps need
+        t0 = time.perf_counter()
+        res = r.first_hits(0, H, shadow=a.shadow_map is not None, normal=a.normal_map is not None)
+        torch.cuda.synchronize(dev)
+        times["first_hits_ms"] = (time.perf_counter() - t0) * 1e3
+        planes = {k: v.cpu().numpy() for k, v in res.items()}
+        info = scene.info()
+        hits = {"objects_hit": int(np.unique(planes["object"][planes["object"] >= 0]).size)}
+        for path, grey in hit_maps(a, planes, info["objects"], info["lights"]):
+            write_png(path, grey if grey.ndim == 3 else np.repeat(grey[..., None], 4, axis=-1), channels=3)
     if rank == 0:
         t0 = time.perf_counter()
         host = frame.cpu().numpy()
@@ -203,7 +279,8 @@ def render(a) -> dict:
         dist.destroy_process_group()
     return {"output": a.output, "width": W, "height": H, "time": a.t, "gpus": world,
             **{k: round(v, 3) for k, v in times.items()}, **({"aa_rays": aa_rays} if a.antialias else {}),
-            **({"rays": rays, "rays_per_pixel": round(rays["total"] / (W * H), 3)} if rays is not None else {})}
+            **({"rays": rays, "rays_per_pixel": round(rays["total"] / (W * H), 3)} if rays is not None else {}),
+            **(hits or {})}
 
 
 def main(argv=None) -> int:

@@ -62,6 +62,14 @@ class rt_ray_counts(ctypes.Structure):
                 ("refract", ctypes.c_uint64)]
 
 
+class rt_hit_planes(ctypes.Structure):
+    """rt_first_hits' output planes: a pointer (an address, or None) and a row stride in bytes each."""
+    _fields_ = [("object", ctypes.c_void_p), ("object_stride", ctypes.c_size_t),
+                ("distance", ctypes.c_void_p), ("distance_stride", ctypes.c_size_t),
+                ("shadow", ctypes.c_void_p), ("shadow_stride", ctypes.c_size_t),
+                ("normal", ctypes.c_void_p), ("normal_stride", ctypes.c_size_t)]
+
+
 _P = ctypes.c_void_p
 _D3 = ctypes.POINTER(ctypes.c_double)
 _XF = ctypes.POINTER(rt_transformation)
@@ -144,6 +152,9 @@ SIGNATURES = {
     "rt_count_rays_row_bands": (_I, [_P, _U32, _U32, _U32, _U32, ctypes.c_int32, ctypes.POINTER(rt_ray_counts), _P, _P,
                                      ctypes.c_size_t, _P]),
     "rt_count_rays": (_I, [_P, _U32, _U32, ctypes.c_int32, ctypes.POINTER(rt_ray_counts), _P, _P, ctypes.c_size_t, _P]),
+    "rt_first_hits": (_I, [_P, _U32, _U32, ctypes.POINTER(rt_hit_planes), _P]),
+    "rt_first_hits_row_bands": (_I, [_P, _U32, _U32, _U32, _U32, ctypes.POINTER(rt_hit_planes), _P]),
+    "rt_first_hits_points": (_I, [_P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
     "rt_ctx_last_kernel_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
     "rt_ctx_synchronize": (_I, [_P]),
     "rt_ctx_set_option": (_I, [_P, ctypes.c_int32, ctypes.c_int32]),

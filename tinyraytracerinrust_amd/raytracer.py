@@ -537,6 +537,86 @@ class Renderer:
         return self._count(lib().rt_count_rays_row_bands, (int(y_first), int(band_rows), int(band_pitch), int(n_bands)),
                            int(band_rows) * int(n_bands), max_depth, rows, pixels, out_rows, out_pixels, stream, totals)
 
+    # rt_hit_planes in field order: (name, dtype, trailing shape after (rows, W))
+    _HIT_PLANES = (("object", "int32", ()), ("distance", "float64", ()), ("shadow", "uint32", ()),
+                   ("normal", "float64", (3,)))
+
+    def _first_hits(self, fn, geometry, n: int, shadow, normal, out, stream) -> dict:
+        """The shared half of first_hits / first_hits_row_bands: ``n`` packed rows, ``geometry`` the call's
+        leading arguments."""
+        out = dict(out or {})
+        unknown = set(out) - {name for name, _, _ in self._HIT_PLANES}
+        if unknown:
+            raise ValueError(f"unknown first-hit planes {sorted(unknown)}")
+        want = {"object": True, "distance": True, "shadow": bool(shadow) or "shadow" in out,
+                "normal": bool(normal) or "normal" in out}
+        made = [name for name, _, _ in self._HIT_PLANES if want[name] and out.get(name) is None]
+        st = stream.cuda_stream if stream is not None else 0
+        if made or any(a is not None and not isinstance(a, np.ndarray) for a in out.values()):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if stream is None:
+                st = torch.cuda.current_stream(dev).cuda_stream
+        planes = _lib.rt_hit_planes()
+        res = {}
+        for name, dtype, tail in self._HIT_PLANES:
+            if not want[name]:
+                continue
+            a = out.get(name)
+            shape = (self.width,) + tail
+            if a is None:
+                a = torch.empty((n,) + shape, dtype=getattr(torch, dtype), device=dev)
+            elif a.shape[0] < n or tuple(a.shape[1:]) != shape:
+                raise ValueError(f"{name} plane {tuple(a.shape)} holds fewer than {n} rows of {shape}")
+            _check_rows(a, dtype, f"{name} plane")
+            res[name] = a
+            if a.shape[0] == 0:
+                continue
+            host = isinstance(a, np.ndarray)
+            setattr(planes, name, a.ctypes.data if host else a.data_ptr())
+            setattr(planes, name + "_stride", a.strides[0] if host else a.stride(0) * a.element_size())
+        if n > 0:
+            check(fn(self.h, *geometry, ctypes.byref(planes), ctypes.c_void_p(st)))
+        return res
+
+    def first_hits(self, y0: int = 0, y1: Optional[int] = None, shadow: bool = False, normal: bool = False, out=None,
+                   stream=None) -> dict:
+        """rt_first_hits: what is under every pixel of rows [y0, y1) (default: the whole frame) before any
+        shading.  A dict of ``"object"`` (rows, W) int32 -- the draw index of the camera ray's nearest hit, -1 on a
+        miss -- and ``"distance"`` (rows, W) float64 (inf on a miss); with ``shadow`` also ``"shadow"`` (rows, W)
+        uint32, bit k set when light k's shadow ray from the hit point is occluded; with ``normal`` ``"normal"``
+        (rows, W, 3) float64, the shape's raw get_normal (not normalised; zeros on a miss).  The arrays are torch
+        tensors on this device, written asynchronously on ``stream`` (torch's current stream), or the arrays of
+        ``out``: a dict by those names of numpy arrays or torch device tensors (a numpy array makes the call
+        synchronous; naming a plane in ``out`` asks for it)."""
+        y1 = self.height if y1 is None else y1
+        return self._first_hits(lib().rt_first_hits, (int(y0), int(y1)), max(int(y1) - int(y0), 0), shadow, normal,
+                                out, stream)
+
+    def first_hits_row_bands(self, y_first: int, band_rows: int, band_pitch: int, n_bands: int, shadow: bool = False,
+                             normal: bool = False, out=None, stream=None) -> dict:
+        """rt_first_hits_row_bands: first_hits for the rows of a band layout (the geometry of render_row_bands).
+        The arrays hold the rows PACKED, band b row j at row b*band_rows + j of n_bands*band_rows rows; rows past
+        the frame's height are not written."""
+        return self._first_hits(lib().rt_first_hits_row_bands,
+                                (int(y_first), int(band_rows), int(band_pitch), int(n_bands)),
+                                int(band_rows) * int(n_bands), shadow, normal, out, stream)
+
+    def first_hits_points(self, xy, shadow: bool = False, normal: bool = False) -> dict:
+        """rt_first_hits_points: the same at sample positions ``xy`` (n, 2), fractional allowed, as numpy arrays:
+        ``"object"`` (n,) int32, ``"distance"`` (n,) float64, with ``shadow`` ``"shadow"`` (n,) uint32, with
+        ``normal`` ``"normal"`` (n, 3) float64.  Synchronous."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        n = xy.shape[0]
+        res = {"object": np.full(n, -1, np.int32), "distance": np.full(n, np.inf, np.float64)}
+        if shadow:
+            res["shadow"] = np.zeros(n, np.uint32)
+        if normal:
+            res["normal"] = np.zeros((n, 3), np.float64)
+        ptr = [ctypes.c_void_p(res[k].ctypes.data) if k in res else None for k, _, _ in self._HIT_PLANES]
+        check(lib().rt_first_hits_points(self.h, ctypes.c_void_p(xy.ctypes.data), n, *ptr, None))
+        return res
+
     def record_rays(self, x: float, y: float, max_depth: int = -1, cap: int = 1 << 17):
         """rt_record_rays: (records as a RAY_RECORD_DTYPE array in callback order, pixel colour)."""
         buf = np.zeros(cap, RAY_RECORD_DTYPE)
@@ -839,6 +919,17 @@ class RayTracer:
         """The whole frame's ray counts at this tracer's max_depth (Renderer.count_rays): the reference's
         algorithmic counts -- primary, shadow, reflect, refract and their total."""
         return self.renderer.count_rays(0, self.height, self.max_depth, rows=rows, pixels=pixels)
+
+    def first_hits(self, shadow: bool = False, normal: bool = False) -> dict:
+        """The whole frame's first-hit maps (Renderer.first_hits): per pixel the object under it, its distance
+        and, on request, the occluded-light bits and the shape's raw normal."""
+        return self.renderer.first_hits(0, self.height, shadow=shadow, normal=normal)
+
+    def pick(self, x: float, y: float) -> Tuple[int, float]:
+        """(object, distance) under the sample position (x, y): the draw index of the camera ray's nearest hit
+        and its distance, (-1, inf) on a miss (Renderer.first_hits_points)."""
+        res = self.renderer.first_hits_points(np.array([[x, y]], np.float64))
+        return int(res["object"][0]), float(res["distance"][0])
 
     def render_orthogonal_view_line(self, y: int, ortho_axes: "OrthoAxes") -> np.ndarray:
         """DebugWindow::render_orthogonal_view_line (debug_window.rs:166-227): (W, 4) f64 colours."""
