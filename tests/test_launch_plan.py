@@ -1,9 +1,9 @@
-"""The row launches' decisions (tinyraytracerinrust_amd/csrc/launch_plan.h: band_geometry, plan_row_launch,
+"""The launches' decisions (tinyraytracerinrust_amd/csrc/launch_plan.h: band_geometry, clamp_bands, plan_row_launch,
 order_from_costs) are pure host code; a stand-alone program includes the header, is built with the address and
 undefined-behaviour sanitizers and checks one section per test: the rule table of the kernel choice, the
 plan's invariants over the product of its inputs, the tile orders on the smallest vectors that take each
-branch, and the band checks' messages.  The GPU tests pin the same choices end to end through
-rt_ctx_kernel_info."""
+branch, the band checks' messages, and the side entries' clamped layouts.  The GPU tests pin the same choices
+end to end through rt_ctx_kernel_info."""
 import pathlib
 import shutil
 import subprocess
@@ -336,6 +336,66 @@ static void geometry() {
   CHECK(rejected(band_geometry(64, 48, 4000000000u, 4000000000u, 3, 2), "band pitch 3 < band rows 4000000000"));
 }
 
+// The side entries' band rule.  band_row is rt_bodies.h's formula, restated here (device code is not included):
+// which frame row the kernels read packed row r of the clamped layout from.
+static uint32_t band_row(const BandGeometry& g, uint32_t r) {
+  return g.band_rows >= g.n_rows ? g.y_first + r : g.y_first + (r / g.band_rows) * g.band_pitch + r % g.band_rows;
+}
+static long clamp() {
+  long accepted = 0;
+  // every accepted layout: the kernels' packed rows are exactly the caller's rows below H, at the caller's packed
+  // places (band b row j at b * band_rows + j), in order
+  for (int H = 1; H <= 13; ++H) for (uint32_t y0 = 0; y0 <= 14; ++y0) for (uint32_t br = 0; br <= 5; ++br)
+  for (uint32_t bp = 0; bp <= 7; ++bp) for (uint32_t nb = 0; nb <= 4; ++nb) {
+    const BandGeometry g = clamp_bands(65, H, y0, br, bp, nb);
+    if (br == 0 || nb == 0) { CHECK(g.status == BandGeometry::NOTHING); continue; }
+    if (bp < br && nb > 1) { CHECK(g.status == BandGeometry::REJECTED); continue; }
+    if (y0 >= (uint32_t)H) { CHECK(g.status == BandGeometry::REJECTED); continue; }
+    CHECK(g.status == BandGeometry::OK && g.n_rows > 0);
+    if (g.status != BandGeometry::OK) continue;
+    ++accepted;
+    uint32_t r = 0;
+    bool same = true;
+    for (uint32_t b = 0; b < nb; ++b)
+      for (uint32_t j = 0; j < br; ++j) {
+        const uint32_t y = y0 + b * bp + j;
+        if (y >= (uint32_t)H) continue;
+        same = same && r < g.n_rows && r == b * br + j && band_row(g, r) == y;
+        ++r;
+      }
+    CHECK(same && r == g.n_rows);
+    CHECK(g.tiles_x == 9 && g.tiles_y == (int)(g.n_rows + 7) / 8 && g.n_tiles == (size_t)g.tiles_x * g.tiles_y);
+    if (fails > 20) return accepted;
+  }
+  // the three statuses, both messages, and the order of the checks (as band_geometry's)
+  CHECK(clamp_bands(64, 48, 0, 0, 4, 2).status == BandGeometry::NOTHING);
+  CHECK(clamp_bands(64, 48, 0, 4, 4, 0).status == BandGeometry::NOTHING);
+  CHECK(clamp_bands(64, 48, 99, 0, 0, 0).status == BandGeometry::NOTHING);       // (ahead of every other check)
+  CHECK(!strcmp(clamp_bands(64, 48, 0, 4, 4, 0).error, "no rows"));
+  CHECK(rejected(clamp_bands(64, 48, 0, 4, 2, 2), "band pitch 2 < band rows 4"));
+  CHECK(rejected(clamp_bands(64, 48, 99, 4, 2, 2), "band pitch 2 < band rows 4"));   // (ahead of the first row's)
+  CHECK(clamp_bands(64, 48, 0, 4, 2, 1).status == BandGeometry::OK);             // one band: the pitch is not read
+  CHECK(rejected(clamp_bands(64, 48, 48, 4, 4, 1), "first row 48 >= height 48"));
+  CHECK(rejected(clamp_bands(64, 48, 4000000000u, 4000000000u, 3, 2), "band pitch 3 < band rows 4000000000"));
+  // rt_antialias' call: one band of more rows than any frame has
+  for (int H : {1, 7, 48, 65535}) {
+    const BandGeometry g = clamp_bands(64, H, 0, UINT32_MAX, UINT32_MAX, 1);
+    CHECK(g.status == BandGeometry::OK && g.y_first == 0 && g.band_rows == (uint32_t)H && g.band_pitch == (uint32_t)H && g.n_rows == (uint32_t)H);
+  }
+  // more bands than any frame has, from the last row: one row
+  BandGeometry g = clamp_bands(64, 48, 47, 1, 1, UINT32_MAX);
+  CHECK(g.status == BandGeometry::OK && g.y_first == 47 && g.band_rows == 1 && g.band_pitch == 1 && g.n_rows == 1);
+  // a cut layout as the kernels receive it: rows 3-6, 11-14, 19-20 of 21
+  g = clamp_bands(41, 21, 3, 4, 8, 5);
+  CHECK(g.status == BandGeometry::OK && g.y_first == 3 && g.band_rows == 4 && g.band_pitch == 8 && g.n_rows == 10);
+  CHECK(band_row(g, 3) == 6 && band_row(g, 4) == 11 && band_row(g, 9) == 20);
+  // the 8x8 tiles of a 65-wide, 9-row layout
+  g = clamp_bands(65, 48, 8, 3, 5, 3);
+  CHECK(g.status == BandGeometry::OK && g.n_rows == 9 && g.tiles_x == 9 && g.tiles_y == 2 && g.n_tiles == 18);
+  CHECK(RT_TILE_W == 8);                                                         // (what the literals above assume)
+  return accepted;
+}
+
 int main(int argc, char** argv) {
   const char* what = argc > 1 ? argv[1] : "";
   long n = 0;
@@ -343,6 +403,7 @@ int main(int argc, char** argv) {
   else if (!strcmp(what, "invariants")) n = invariants();
   else if (!strcmp(what, "orders")) orders();
   else if (!strcmp(what, "geometry")) geometry();
+  else if (!strcmp(what, "clamp")) n = clamp();
   else return 2;
   printf("%s: %d failures, %ld cases\n", what, fails, n);
   return fails != 0;
@@ -393,3 +454,10 @@ def test_band_geometry(harness):
     """Every rejected band launch keeps its message; 2^24 rows pass, one more does not; zero rows or bands
     are reported as nothing to do."""
     run(harness, "geometry")
+
+
+def test_clamp_bands(harness):
+    """The side entries' band rule over H 1..13, y_first 0..14, band_rows 0..5, band_pitch 0..7, n_bands 0..4:
+    every accepted layout's packed rows are, through the kernels' band_row, exactly the caller's rows below H at
+    the caller's packed places, and there is at least one; the statuses and messages; rt_antialias' one huge band."""
+    assert run(harness, "clamp") >= 10000

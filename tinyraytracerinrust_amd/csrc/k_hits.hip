@@ -3,8 +3,6 @@
 // lights' shadow rays are occluded there and the shape's raw normal -- the questions a host asks about a frame
 // before any shading (picking, depth / id / normal passes, shadow overlays).  The per-sample function is
 // rt_hits.h's first_hit: the render kernels' own walks, nothing of their shading, nothing that recurses.
-#include <algorithm>
-
 #include "rt_device.h"
 #include "rt_hits.h"
 #include "rt_ctx.h"
@@ -109,72 +107,39 @@ static int hits_scene_ok(rt_ctx* c, bool shadow) {
   return RT_OK;
 }
 
-// The rows of a band layout, checked and clamped as rt_count_rays_row_bands does (k_stats.hip count_rows): the
-// kernel sees n_rows packed rows that all exist.
+// The rows of a band layout, cut to the frame by clamp_bands (launch_plan.h): the kernel sees n_rows packed rows
+// that all exist.
 static int hits_rows(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
                      const rt_hit_planes* out, void* stream) {
   if (!c || !out || (!out->object && !out->distance && !out->shadow && !out->normal)) return fail(RT_ERR_INVALID, "null argument");
   RT_TRY(hits_scene_ok(c, out->shadow != nullptr));
-  const int W = c->dev.width, H = c->dev.height;
+  const int W = c->dev.width;
   struct Plane { void* p; size_t stride, px; const char* what; };
   const Plane pl[4] = {{out->object, out->object_stride, 4, "object"}, {out->distance, out->distance_stride, 8, "distance"},
                        {out->shadow, out->shadow_stride, 4, "shadow"}, {out->normal, out->normal_stride, 24, "normal"}};
   for (const Plane& q : pl)
     if (q.p && q.stride < q.px * (size_t)W) return fail(RT_ERR_INVALID, "%s stride %zu < %zu", q.what, q.stride, q.px * (size_t)W);
-  if (band_rows == 0 || n_bands == 0) return RT_OK;
-  if (band_pitch < band_rows && n_bands > 1) return fail(RT_ERR_INVALID, "band pitch %u < band rows %u", band_pitch, band_rows);
-  if (y_first >= (uint32_t)H) return fail(RT_ERR_INVALID, "first row %u >= height %d", y_first, H);
-  if (n_bands > 1) n_bands = std::min(n_bands, ((uint32_t)H - 1 - y_first) / band_pitch + 1);
-  const uint32_t last_rows = std::min(band_rows, (uint32_t)H - (y_first + (n_bands - 1) * band_pitch));
-  if (n_bands == 1) band_rows = band_pitch = last_rows;
-  const uint32_t n_rows = (n_bands - 1) * band_rows + last_rows;
-  const size_t n_tiles = (size_t)((W + RT_TILE_W - 1) / RT_TILE_W) * ((n_rows + RT_TILE_H - 1) / RT_TILE_H);
-  if (n_tiles == 0 || n_tiles > (size_t)INT32_MAX) return fail(RT_ERR_INVALID, "bad first-hit launch of %zu tiles", n_tiles);
+  const BandGeometry g = clamp_bands(W, c->dev.height, y_first, band_rows, band_pitch, n_bands);
+  if (g.status == BandGeometry::NOTHING) return RT_OK;
+  if (g.status != BandGeometry::OK) return fail(RT_ERR_INVALID, "%s", g.error);
+  if (g.n_tiles == 0 || g.n_tiles > (size_t)INT32_MAX) return fail(RT_ERR_INVALID, "bad first-hit launch of %zu tiles", g.n_tiles);
   RT_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;   // NULL = the device's default stream
   // device planes are written in place (element-aligned rows); host planes are staged, packed, in the scratch
-  bool dev[4];
-  size_t off = 0, o_stage[4] = {0, 0, 0, 0};
-  for (int k = 0; k < 4; ++k) {
-    dev[k] = !pl[k].p || is_device_ptr(pl[k].p);
-    const size_t align = pl[k].px == 4 ? 4 : 8;
-    if (pl[k].p && dev[k] && (((uintptr_t)pl[k].p | pl[k].stride) & (align - 1)))
-      return fail(RT_ERR_INVALID, "%s rows must be %zu-byte aligned", pl[k].what, align);
-    if (!dev[k]) {
-      o_stage[k] = off;
-      off = (off + pl[k].px * (size_t)W * n_rows + 255) & ~(size_t)255;
-    }
-  }
-  if (off) RT_TRY(ensure_scratch(c, off));
-  uint8_t* sb = (uint8_t*)c->scratch;
-  uint8_t* kp[4];
-  size_t ks[4];
-  for (int k = 0; k < 4; ++k) {
-    kp[k] = !pl[k].p ? nullptr : dev[k] ? (uint8_t*)pl[k].p : sb + o_stage[k];
-    ks[k] = dev[k] ? pl[k].stride : pl[k].px * (size_t)W;
-  }
-  const HitPlanes P = {kp[0], ks[0], kp[1], ks[1], kp[2], ks[2], kp[3], ks[3]};
-  const dim3 grid((unsigned)n_tiles);
-  const int a0 = (int)y_first, a1 = (int)band_rows, a2 = (int)band_pitch, a3 = (int)n_rows;
-  if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
+  Stager sg;
+  for (const Plane& q : pl) sg.add_out(q.p, q.stride, q.px * (size_t)W, g.n_rows, q.px == 4 ? 4 : 8, q.what);
+  RT_TRY(sg.reserve(c, st));
+  const HitPlanes P = {sg.ptr(0), sg.stride(0), sg.ptr(1), sg.stride(1), sg.ptr(2), sg.stride(2), sg.ptr(3), sg.stride(3)};
+  const dim3 grid((unsigned)g.n_tiles);
+  const int a0 = (int)g.y_first, a1 = (int)g.band_rows, a2 = (int)g.band_pitch, a3 = (int)g.n_rows;
+  RT_TRY(begin_launch(c, st));
   with_hit_flags(c->dev.any_transparent != 0, P.shadow != nullptr, P.normal != nullptr, c->views.kind != 0,
                  [&](auto R, auto Sh, auto N, auto V) {
     hipLaunchKernelGGL((first_hits_kernel<decltype(R)::value, decltype(Sh)::value, decltype(N)::value, decltype(V)::value>),
                        grid, dim3(64), 0, st, c->dev, c->views, a0, a1, a2, a3, P);
   });
-  RT_HIP(hipGetLastError());
-  if (c->timing) RT_HIP(hipEventRecord(c->ev1, st));
-  c->timed = c->timing;
-  RT_TRY(mark_launch(c, st));
-  bool staged = false;
-  for (int k = 0; k < 4; ++k) {
-    if (dev[k]) continue;
-    const size_t row = pl[k].px * (size_t)W;
-    RT_HIP(hipMemcpy2DAsync(pl[k].p, pl[k].stride, kp[k], row, row, n_rows, hipMemcpyDeviceToHost, st));
-    staged = true;
-  }
-  if (staged) RT_HIP(hipStreamSynchronize(st));
-  return RT_OK;
+  RT_TRY(end_launch(c, st));
+  return sg.finish(st, false);
 }
 
 extern "C" {
@@ -199,49 +164,25 @@ int rt_first_hits_points(rt_ctx* c, const double* xy, size_t n, int32_t* object,
   if (n > (size_t)INT32_MAX) return fail(RT_ERR_INVALID, "%zu sample positions > %d", n, INT32_MAX);
   RT_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;   // NULL = the device's default stream
-  // staging for host pointers: [xy][object][distance][shadow][normal], each 256-byte aligned
+  // device arrays are read and written in place (element-aligned); host arrays are staged in the scratch
   void* const outs[4] = {object, distance, shadow, normal};
   const size_t px[4] = {4, 8, 4, 24};
-  const bool dev_in = is_device_ptr(xy);
-  bool dev[4];
-  size_t off = 0, o_stage[4] = {0, 0, 0, 0};
-  auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_xy = dev_in ? 0 : take(n * 16);
-  for (int k = 0; k < 4; ++k) {
-    dev[k] = !outs[k] || is_device_ptr(outs[k]);
-    if (outs[k] && dev[k] && ((uintptr_t)outs[k] & (px[k] == 4 ? 3 : 7))) return fail(RT_ERR_INVALID, "misaligned device output");
-    if (!dev[k]) o_stage[k] = take(n * px[k]);
-  }
-  if (dev_in && ((uintptr_t)xy & 7)) return fail(RT_ERR_INVALID, "misaligned sample positions");
-  if (off) RT_TRY(ensure_scratch(c, off));
-  uint8_t* sb = (uint8_t*)c->scratch;
-  const double* in = xy;
-  if (!dev_in) {
-    RT_HIP(hipMemcpyAsync(sb + o_xy, xy, n * 16, hipMemcpyHostToDevice, st));
-    in = (const double*)(sb + o_xy);
-  }
-  void* kp[4];
-  for (int k = 0; k < 4; ++k) kp[k] = !outs[k] ? nullptr : dev[k] ? outs[k] : (void*)(sb + o_stage[k]);
+  const char* const what[4] = {"object", "distance", "shadow", "normal"};
+  Stager sg;
+  for (int k = 0; k < 4; ++k) sg.add_out(outs[k], n * px[k], n * px[k], 1, px[k] == 4 ? 4 : 8, what[k]);
+  const int k_xy = sg.add_in(xy, n * 16, n * 16, 1, 8, "sample position");
+  RT_TRY(sg.reserve(c, st));
+  const double* in = sg.ptr<const double>(k_xy);
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
+  RT_TRY(begin_launch(c, st));
   with_hit_flags(c->dev.any_transparent != 0, shadow != nullptr, normal != nullptr, c->views.kind != 0,
                  [&](auto R, auto Sh, auto N, auto V) {
     hipLaunchKernelGGL((first_hits_points_kernel<decltype(R)::value, decltype(Sh)::value, decltype(N)::value, decltype(V)::value>),
-                       grid, block, 0, st, c->dev, c->views, in, n, (int32_t*)kp[0], (double*)kp[1], (uint32_t*)kp[2],
-                       (double*)kp[3]);
+                       grid, block, 0, st, c->dev, c->views, in, n, sg.ptr<int32_t>(0), sg.ptr<double>(1), sg.ptr<uint32_t>(2),
+                       sg.ptr<double>(3));
   });
-  RT_HIP(hipGetLastError());
-  if (c->timing) RT_HIP(hipEventRecord(c->ev1, st));
-  c->timed = c->timing;
-  RT_TRY(mark_launch(c, st));
-  bool staged = false;
-  for (int k = 0; k < 4; ++k) {
-    if (dev[k]) continue;
-    RT_HIP(hipMemcpyAsync(outs[k], kp[k], n * px[k], hipMemcpyDeviceToHost, st));
-    staged = true;
-  }
-  if (staged) RT_HIP(hipStreamSynchronize(st));
-  return RT_OK;
+  RT_TRY(end_launch(c, st));
+  return sg.finish(st, false);
 }
 
 }  // extern "C"

@@ -88,16 +88,11 @@ int rt_render_points_f64(rt_ctx* c, const double* xy, size_t n, int32_t max_dept
   if (n == 0) return RT_OK;
   RT_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;   // NULL = the device's default stream
-  const bool dev_in = is_device_ptr(xy), dev_out = is_device_ptr(out);
-  const double* in = xy;
-  double* target = out;
-  if (!dev_in || !dev_out) {
-    int rc = ensure_scratch(c, n * 6 * sizeof(double));
-    if (rc) return rc;
-    double* sx = (double*)c->scratch;
-    if (!dev_in) { RT_HIP(hipMemcpyAsync(sx, xy, n * 2 * sizeof(double), hipMemcpyHostToDevice, st)); in = sx; }
-    if (!dev_out) target = sx + 2 * n;
-  }
+  Stager sg;
+  const int i_in = sg.add_in(xy, n * 16, n * 16, 1, 0, "sample position"), i_out = sg.add_out(out, n * 32, n * 32, 1, 0, "output");
+  RT_TRY(sg.reserve(c, st));
+  const double* in = sg.ptr<const double>(i_in);
+  double* target = sg.ptr<double>(i_out);
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
   // the scene's specialised points kernel (spec_text.cpp rt_spec_points: one-wave workgroups), once it is loaded;
   // a launch of 2^31 samples or more keeps the generic kernel (the module launch's work size is 32 bits)
@@ -106,7 +101,7 @@ int rt_render_points_f64(rt_ctx* c, const double* xy, size_t n, int32_t max_dept
     sfn = nullptr;
     c->spec.last_sample = "points";
   }
-  if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
+  RT_TRY(begin_launch(c, st));
   if (sfn) {
     int depth = max_depth;
     void* kargs[] = {&c->dev, (void*)&in, &n, &depth, &target};
@@ -118,15 +113,8 @@ int rt_render_points_f64(rt_ctx* c, const double* xy, size_t n, int32_t max_dept
     hipLaunchKernelGGL((render_points_views_kernel<false>), grid, block, 0, st, c->dev, c->views, in, n, max_depth, target);
   else if (c->dev.any_transparent) hipLaunchKernelGGL((render_points_kernel<true>), grid, block, 0, st, c->dev, in, n, max_depth, target);
   else hipLaunchKernelGGL((render_points_kernel<false>), grid, block, 0, st, c->dev, in, n, max_depth, target);
-  RT_HIP(hipGetLastError());
-  if (c->timing) RT_HIP(hipEventRecord(c->ev1, st));
-  c->timed = c->timing;
-  RT_TRY(rt::mark_launch(c, st));
-  if (!dev_out) {
-    RT_HIP(hipMemcpyAsync(out, target, n * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-    RT_HIP(hipStreamSynchronize(st));
-  }
-  return RT_OK;
+  RT_TRY(end_launch(c, st));
+  return sg.finish(st, false);
 }
 
 }  // extern "C"

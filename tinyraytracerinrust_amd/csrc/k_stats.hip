@@ -4,8 +4,6 @@
 // :359-363; the CPU oracle's C_RAY_* counters), not what the culling render kernels execute: the kernel walks
 // every pixel's ray tree with trace() and a recorder that only counts.  The traced colour is never stored, so
 // whatever feeds the colour alone is dead code to the compiler; nothing here relies on that.
-#include <algorithm>
-
 #include "rt_device.h"
 #include "rt_ctx.h"
 
@@ -110,8 +108,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RT_WAVES(REF
 
 using namespace rt;
 
-// The rows of a band layout, checked and clamped as rt_antialias_row_bands does (k_views.hip antialias_rows): the
-// kernel sees n_rows packed rows that all exist.
+// The rows of a band layout, cut to the frame by clamp_bands (launch_plan.h): the kernel sees n_rows packed rows
+// that all exist.
 static int count_rows(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
                       int32_t max_depth, rt_ray_counts* totals, uint64_t* row_counts, uint32_t* pixel_counts,
                       size_t pixel_stride, void* stream) {
@@ -119,58 +117,41 @@ static int count_rows(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t 
   if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
   if (max_depth < 0) max_depth = c->max_depth;
   if (max_depth > RT_MAX_DEPTH_CAP) return fail(RT_ERR_UNSUPPORTED, "max_depth %d > %d", max_depth, RT_MAX_DEPTH_CAP);
-  const int W = c->dev.width, H = c->dev.height;
+  const int W = c->dev.width;
   const size_t row16 = (size_t)W * 16;
   if (pixel_counts && pixel_stride < row16) return fail(RT_ERR_INVALID, "pixel stride %zu < %zu", pixel_stride, row16);
   if (totals) *totals = {0, 0, 0, 0};
-  if (band_rows == 0 || n_bands == 0) return RT_OK;
-  if (band_pitch < band_rows && n_bands > 1) return fail(RT_ERR_INVALID, "band pitch %u < band rows %u", band_pitch, band_rows);
-  if (y_first >= (uint32_t)H) return fail(RT_ERR_INVALID, "first row %u >= height %d", y_first, H);
-  if (n_bands > 1) n_bands = std::min(n_bands, ((uint32_t)H - 1 - y_first) / band_pitch + 1);
-  const uint32_t last_rows = std::min(band_rows, (uint32_t)H - (y_first + (n_bands - 1) * band_pitch));
-  if (n_bands == 1) band_rows = band_pitch = last_rows;
-  const uint32_t n_rows = (n_bands - 1) * band_rows + last_rows;
-  const size_t n_tiles = (size_t)((W + RT_TILE_W - 1) / RT_TILE_W) * ((n_rows + RT_TILE_H - 1) / RT_TILE_H);
-  if (n_tiles == 0 || n_tiles > (size_t)INT32_MAX) return fail(RT_ERR_INVALID, "bad count launch of %zu tiles", n_tiles);
+  const BandGeometry g = clamp_bands(W, c->dev.height, y_first, band_rows, band_pitch, n_bands);
+  if (g.status == BandGeometry::NOTHING) return RT_OK;
+  if (g.status != BandGeometry::OK) return fail(RT_ERR_INVALID, "%s", g.error);
+  if (g.n_tiles == 0 || g.n_tiles > (size_t)INT32_MAX) return fail(RT_ERR_INVALID, "bad count launch of %zu tiles", g.n_tiles);
   RT_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;   // NULL = the device's default stream
-  const bool d_rows = !row_counts || is_device_ptr(row_counts), d_px = !pixel_counts || is_device_ptr(pixel_counts);
-  if (row_counts && d_rows && ((uintptr_t)row_counts & 7)) return fail(RT_ERR_INVALID, "row counts must be 8-byte aligned");
-  if (pixel_counts && d_px && (((uintptr_t)pixel_counts | pixel_stride) & 15))
-    return fail(RT_ERR_INVALID, "pixel count rows must be 16-byte aligned");
-  // device staging: [the totals' slots][row sums][pixel counts], the last two for host pointers
-  const size_t rows_bytes = (size_t)n_rows * 32;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-  const size_t tot_bytes = (size_t)RT_COUNT_SLOTS * 32;
-  const size_t o_tot = totals ? take(tot_bytes) : 0, o_rows = d_rows ? 0 : take(rows_bytes), o_px = d_px ? 0 : take(row16 * n_rows);
-  if (off) RT_TRY(ensure_scratch(c, off));
-  uint8_t* sb = (uint8_t*)c->scratch;
-  unsigned long long* k_tot = totals ? (unsigned long long*)(sb + o_tot) : nullptr;
-  unsigned long long* k_rows = row_counts ? (unsigned long long*)(d_rows ? (uint8_t*)row_counts : sb + o_rows) : nullptr;
-  uint8_t* k_px = pixel_counts ? (d_px ? (uint8_t*)pixel_counts : sb + o_px) : nullptr;
-  const size_t k_stride = d_px ? pixel_stride : row16;
+  // the row sums and the pixel counts in place or staged; the totals' slots always in the scratch
+  const size_t rows_bytes = (size_t)g.n_rows * 32, tot_bytes = (size_t)RT_COUNT_SLOTS * 32;
+  Stager sg;
+  const int i_rows = sg.add_out(row_counts, rows_bytes, rows_bytes, 1, 8, "row count");
+  const int i_px = sg.add_out(pixel_counts, pixel_stride, row16, g.n_rows, 16, "pixel count");
+  const int i_tot = totals ? sg.add_scratch(tot_bytes) : -1;
+  RT_TRY(sg.reserve(c, st));
+  unsigned long long* k_tot = totals ? sg.ptr<unsigned long long>(i_tot) : nullptr;
+  unsigned long long* k_rows = sg.ptr<unsigned long long>(i_rows);
   // the sums start at zero, ahead of the timing event: rt_ctx_last_kernel_ms reports the kernel alone
   if (k_tot) RT_HIP(hipMemsetAsync(k_tot, 0, tot_bytes, st));
   if (k_rows) RT_HIP(hipMemsetAsync(k_rows, 0, rows_bytes, st));
-  const dim3 grid((unsigned)n_tiles);
-  const int a0 = (int)y_first, a1 = (int)band_rows, a2 = (int)band_pitch, a3 = (int)n_rows;
-  if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
+  const dim3 grid((unsigned)g.n_tiles);
+  const int a0 = (int)g.y_first, a1 = (int)g.band_rows, a2 = (int)g.band_pitch, a3 = (int)g.n_rows;
+  RT_TRY(begin_launch(c, st));
   with_bool(c->dev.any_transparent != 0, [&](auto R) {
     with_bool(c->views.kind != 0, [&](auto V) {
       hipLaunchKernelGGL((count_rays_kernel<decltype(R)::value, decltype(V)::value>), grid, dim3(64), 0, st, c->dev, c->views,
-                         a0, a1, a2, a3, (int)max_depth, k_tot, k_rows, k_px, k_stride);
+                         a0, a1, a2, a3, (int)max_depth, k_tot, k_rows, sg.ptr(i_px), sg.stride(i_px));
     });
   });
-  RT_HIP(hipGetLastError());
-  if (c->timing) RT_HIP(hipEventRecord(c->ev1, st));
-  c->timed = c->timing;
-  RT_TRY(mark_launch(c, st));
+  RT_TRY(end_launch(c, st));
   std::vector<unsigned long long> slots(totals ? (size_t)RT_COUNT_SLOTS * 4 : 0);
   if (totals) RT_HIP(hipMemcpyAsync(slots.data(), k_tot, tot_bytes, hipMemcpyDeviceToHost, st));
-  if (!d_rows) RT_HIP(hipMemcpyAsync(row_counts, k_rows, rows_bytes, hipMemcpyDeviceToHost, st));
-  if (!d_px) RT_HIP(hipMemcpy2DAsync(pixel_counts, pixel_stride, k_px, row16, row16, n_rows, hipMemcpyDeviceToHost, st));
-  if (totals || !d_rows || !d_px) RT_HIP(hipStreamSynchronize(st));
+  RT_TRY(sg.finish(st, totals != nullptr));
   if (totals)
     for (size_t i = 0; i < slots.size(); i += 4) {
       totals->primary += slots[i]; totals->shadow += slots[i + 1]; totals->reflect += slots[i + 2]; totals->refract += slots[i + 3];

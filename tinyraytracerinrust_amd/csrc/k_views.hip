@@ -430,7 +430,7 @@ int rt_assemble_row_bands_rgb8(const uint8_t* gathered, size_t gathered_stride, 
 }
 
 // antialiaser.rs:87-191 over the rows of a band layout of a whole quantised frame (see the kernels above):
-// rt_antialias passes one band of more rows than any frame has, which the clamp to H below makes the layout
+// rt_antialias passes one band of more rows than any frame has, which clamp_bands (launch_plan.h) makes the layout
 // (0, H, H, 1); rt_antialias_row_bands passes its caller's.  `who` names the entry in the one error text that does.
 static int antialias_rows(rt_ctx* c, const char* who, const uint8_t* src_rgba8, size_t src_stride, double threshold,
                           int32_t level, int32_t max_depth, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch,
@@ -450,19 +450,14 @@ static int antialias_rows(rt_ctx* c, const char* who, const uint8_t* src_rgba8, 
   if (src_stride < row4) return fail(RT_ERR_INVALID, "source stride %zu < %zu", src_stride, row4);
   if (dst_rgba8 && dst_stride < row4) return fail(RT_ERR_INVALID, "output stride %zu < %zu", dst_stride, row4);
   if (dst_f64 && f64_stride < row32) return fail(RT_ERR_INVALID, "f64 stride %zu < %zu", f64_stride, row32);
-  // the owned rows, as rt_render_row_bands reads its geometry; bands that start at or past H and the last band's
-  // rows past H are dropped here, so the kernels see n_rows packed rows that all exist
-  if (band_rows == 0 || n_bands == 0) {
+  const BandGeometry g = clamp_bands(W, H, y_first, band_rows, band_pitch, n_bands);   // n_rows packed rows that all exist
+  if (g.status == BandGeometry::NOTHING) {
     if (rays_traced) *rays_traced = 0;
     return RT_OK;
   }
-  if (band_pitch < band_rows && n_bands > 1) return fail(RT_ERR_INVALID, "band pitch %u < band rows %u", band_pitch, band_rows);
-  if (y_first >= (uint32_t)H) return fail(RT_ERR_INVALID, "first row %u >= height %d", y_first, H);
-  if (n_bands > 1) n_bands = std::min(n_bands, ((uint32_t)H - 1 - y_first) / band_pitch + 1);
-  const uint32_t last_rows = std::min(band_rows, (uint32_t)H - (y_first + (n_bands - 1) * band_pitch));
-  if (n_bands == 1) band_rows = band_pitch = last_rows;
-  const uint32_t n_rows = (n_bands - 1) * band_rows + last_rows;
-  const AaBands B = {(int)y_first, (int)band_rows, (int)band_pitch, (int)n_rows};
+  if (g.status != BandGeometry::OK) return fail(RT_ERR_INVALID, "%s", g.error);
+  const uint32_t n_rows = g.n_rows;
+  const AaBands B = {(int)g.y_first, (int)g.band_rows, (int)g.band_pitch, (int)n_rows};
   RT_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   // the trace passes' kernel: the scene's specialised one once it is loaded (requested here on the first call
@@ -472,27 +467,23 @@ static int antialias_rows(rt_ctx* c, const char* who, const uint8_t* src_rgba8, 
   const char* const sample_ran = c->spec.last_sample;
   c->spec.last_sample = sample_before;
   const size_t npx = (size_t)W * n_rows;                             // the call's pixels: outputs, edge list
-  // device staging: [src u8, the whole frame][dst u8][dst f64][edges][counters] for host pointers
-  const bool d_src = is_device_ptr(src_rgba8), d_u8 = !dst_rgba8 || is_device_ptr(dst_rgba8);
-  const bool d_f64 = !dst_f64 || is_device_ptr(dst_f64);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_src = d_src ? 0 : take(row4 * H), o_u8 = d_u8 ? 0 : take(npx * 4), o_f64 = d_f64 ? 0 : take(npx * 32);
-  const size_t o_edges = take(npx * 4), o_cnt = take(64);
-  int rc = ensure_scratch(c, off);
-  if (rc) return rc;
-  uint8_t* sb = (uint8_t*)c->scratch;
-  const uint8_t* src = d_src ? src_rgba8 : sb + o_src;
-  size_t sstride = src_stride;
-  if (!d_src) { RT_HIP(hipMemcpy2DAsync(sb + o_src, row4, src_rgba8, src_stride, row4, H, hipMemcpyHostToDevice, st)); sstride = row4; }
-  uint8_t* u8 = dst_rgba8 ? (d_u8 ? dst_rgba8 : sb + o_u8) : nullptr;
-  size_t u8s = d_u8 ? dst_stride : row4;
-  double* f64 = dst_f64 ? (d_f64 ? dst_f64 : (double*)(sb + o_f64)) : nullptr;
-  size_t f64s = d_f64 ? f64_stride : row32;
-  uint32_t* edges = (uint32_t*)(sb + o_edges);
-  uint32_t* cnt = (uint32_t*)(sb + o_cnt);
-  RT_HIP(hipMemsetAsync(cnt, 0, 64, st));
-  if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
+  // the whole source frame and the call's output rows in place or staged; the edge list and the counters
+  Stager sg;
+  const int i_src = sg.add_in(src_rgba8, src_stride, row4, H, 0, "source");
+  const int i_u8 = sg.add_out(dst_rgba8, dst_stride, row4, n_rows, 0, "output");
+  const int i_f64 = sg.add_out(dst_f64, f64_stride, row32, n_rows, 0, "f64");
+  const int i_edges = sg.add_scratch(npx * 4), i_cnt = sg.add_scratch(64);
+  RT_TRY(sg.reserve(c, st));
+  const uint8_t* src = sg.ptr(i_src);
+  const size_t sstride = sg.stride(i_src);
+  uint8_t* u8 = sg.ptr(i_u8);
+  const size_t u8s = sg.stride(i_u8);
+  double* f64 = sg.ptr<double>(i_f64);
+  const size_t f64s = sg.stride(i_f64);
+  uint32_t* edges = sg.ptr<uint32_t>(i_edges);
+  uint32_t* cnt = sg.ptr<uint32_t>(i_cnt);
+  RT_HIP(hipMemsetAsync(cnt, 0, 64, st));   // ahead of the timing event, as the count's sums (k_stats.hip)
+  RT_TRY(begin_launch(c, st));
   const int tiles = ((W + 15) / 16) * (((int)n_rows + 15) / 16);
   hipLaunchKernelGGL(aa_classify_kernel, dim3(tiles), dim3(256), 0, st, src, sstride, W, H, B, threshold, (int)level,
                      u8, u8s, f64, f64s, edges, cnt);
@@ -557,12 +548,8 @@ static int antialias_rows(rt_ctx* c, const char* who, const uint8_t* src_rgba8, 
     (void)hipFreeAsync(work, st);
     if (err) return err;
   }
-  if (c->timing) RT_HIP(hipEventRecord(c->ev1, st));
-  c->timed = c->timing;
-  RT_TRY(rt::mark_launch(c, st));
-  if (dst_rgba8 && !d_u8) RT_HIP(hipMemcpy2DAsync(dst_rgba8, dst_stride, u8, row4, row4, n_rows, hipMemcpyDeviceToHost, st));
-  if (dst_f64 && !d_f64) RT_HIP(hipMemcpy2DAsync(dst_f64, f64_stride, f64, row32, row32, n_rows, hipMemcpyDeviceToHost, st));
-  RT_HIP(hipStreamSynchronize(st));
+  RT_TRY(end_launch(c, st));
+  RT_TRY(sg.finish(st, true));              // (the call has waited for its edge count: it ends synchronous)
   if (rays_traced) *rays_traced = rays;
   return RT_OK;
 }
@@ -595,29 +582,21 @@ int rt_antialias_edges(rt_ctx* c, const uint8_t* src_rgba8, size_t src_stride, d
   if (overlay_stride < row4) return fail(RT_ERR_INVALID, "overlay stride %zu < %zu", overlay_stride, row4);
   RT_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  const bool d_src = is_device_ptr(src_rgba8), d_out = is_device_ptr(overlay_rgba8);
-  if (d_out && (((uintptr_t)overlay_rgba8 | overlay_stride) & 3)) return fail(RT_ERR_INVALID, "overlay rows must be 4-byte aligned");
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_src = d_src ? 0 : take(row4 * H), o_out = d_out ? 0 : take(row4 * H), o_cnt = take(64);
-  int rc = ensure_scratch(c, off);
-  if (rc) return rc;
-  uint8_t* sb = (uint8_t*)c->scratch;
-  const uint8_t* src = d_src ? src_rgba8 : sb + o_src;
-  size_t sstride = src_stride;
-  if (!d_src) { RT_HIP(hipMemcpy2DAsync(sb + o_src, row4, src_rgba8, src_stride, row4, H, hipMemcpyHostToDevice, st)); sstride = row4; }
-  uint8_t* out = d_out ? overlay_rgba8 : sb + o_out;
-  const size_t ostride = d_out ? overlay_stride : row4;
-  uint32_t* cnt = (uint32_t*)(sb + o_cnt);
+  Stager sg;
+  const int i_out = sg.add_out(overlay_rgba8, overlay_stride, row4, H, 4, "overlay");
+  const int i_src = sg.add_in(src_rgba8, src_stride, row4, H, 0, "source");
+  const int i_cnt = sg.add_scratch(64);
+  RT_TRY(sg.reserve(c, st));
+  uint32_t* cnt = sg.ptr<uint32_t>(i_cnt);
   RT_HIP(hipMemsetAsync(cnt, 0, 64, st));
   const int tiles = ((W + 15) / 16) * ((H + 15) / 16);
-  hipLaunchKernelGGL(aa_edges_kernel, dim3(tiles), dim3(256), 0, st, src, sstride, W, H, threshold, out, ostride, cnt);
+  hipLaunchKernelGGL(aa_edges_kernel, dim3(tiles), dim3(256), 0, st, sg.ptr<const uint8_t>(i_src), sg.stride(i_src), W, H, threshold,
+                     sg.ptr(i_out), sg.stride(i_out), cnt);
   RT_HIP(hipGetLastError());
-  RT_TRY(rt::mark_launch(c, st));
-  if (!d_out) RT_HIP(hipMemcpy2DAsync(overlay_rgba8, overlay_stride, out, row4, row4, H, hipMemcpyDeviceToHost, st));
+  RT_TRY(rt::mark_launch(c, st));           // (no timing pair: the overlay is no render)
   uint32_t n = 0;
   if (n_edges) RT_HIP(hipMemcpyAsync(&n, cnt, 4, hipMemcpyDeviceToHost, st));
-  if (n_edges || !d_out || !d_src) RT_HIP(hipStreamSynchronize(st));
+  RT_TRY(sg.finish(st, n_edges != nullptr));
   if (n_edges) *n_edges = n;
   return RT_OK;
 }
@@ -644,28 +623,16 @@ int rt_render_ortho(rt_ctx* c, int32_t axis1, int32_t axis2, double dir1, double
   if (rgba_f64 && f64_stride < row32) return fail(RT_ERR_INVALID, "f64 stride %zu < %zu", f64_stride, row32);
   RT_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  const bool d8 = !rgba8 || is_device_ptr(rgba8), df = !rgba_f64 || is_device_ptr(rgba_f64);
-  uint8_t* t8 = rgba8;
-  double* tf = rgba_f64;
-  size_t s8 = row_stride_bytes, sf = f64_stride;
-  if (!d8 || !df) {
-    int rc = ensure_scratch(c, (d8 ? 0 : row4 * n) + (df ? 0 : row32 * n) + 256);
-    if (rc) return rc;
-    uint8_t* sb = (uint8_t*)c->scratch;
-    if (!d8) { t8 = sb; s8 = row4; sb += (row4 * n + 255) & ~(size_t)255; }
-    if (!df) { tf = (double*)sb; sf = row32; }
-  }
+  Stager sg;
+  const int i8 = sg.add_out(rgba8, row_stride_bytes, row4, n, 0, "output");
+  const int i_f = sg.add_out(rgba_f64, f64_stride, row32, n, 0, "f64");
+  RT_TRY(sg.reserve(c, st));
   const int tiles = ((W + 15) / 16) * (int)((n + 15) / 16);
-  if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
-  hipLaunchKernelGGL(ortho_kernel, dim3(tiles), dim3(256), 0, st, c->dev, V, (int)y0, (int)n, t8, s8, tf, sf);
-  RT_HIP(hipGetLastError());
-  if (c->timing) RT_HIP(hipEventRecord(c->ev1, st));
-  c->timed = c->timing;
-  RT_TRY(rt::mark_launch(c, st));
-  if (!d8) RT_HIP(hipMemcpy2DAsync(rgba8, row_stride_bytes, t8, row4, row4, n, hipMemcpyDeviceToHost, st));
-  if (!df) RT_HIP(hipMemcpy2DAsync(rgba_f64, f64_stride, tf, row32, row32, n, hipMemcpyDeviceToHost, st));
-  if (!d8 || !df) RT_HIP(hipStreamSynchronize(st));
-  return RT_OK;
+  RT_TRY(begin_launch(c, st));
+  hipLaunchKernelGGL(ortho_kernel, dim3(tiles), dim3(256), 0, st, c->dev, V, (int)y0, (int)n, sg.ptr(i8), sg.stride(i8),
+                     sg.ptr<double>(i_f), sg.stride(i_f));
+  RT_TRY(end_launch(c, st));
+  return sg.finish(st, false);
 }
 
 // RayDebugger::record_rays (ray_debugger.rs:92-137): one thread, records in callback order.
@@ -681,14 +648,13 @@ int rt_record_rays(rt_ctx* c, double x, double y, int32_t max_depth, rt_ray_reco
   const bool refr = c->dev.any_transparent != 0;
   const int dev_cap = refr ? (2 << max_depth) - 1 : max_depth + 1;
   const size_t rec_bytes = sizeof(rt_ray_record) * ((size_t)dev_cap + 1);
-  const size_t ord_off = (rec_bytes + 255) & ~(size_t)255, cnt_off = ord_off + (((size_t)dev_cap * 4 + 255) & ~(size_t)255);
-  int rc = ensure_scratch(c, cnt_off + 64);
-  if (rc) return rc;
-  uint8_t* sb = (uint8_t*)c->scratch;
-  rt_ray_record* d_rec = (rt_ray_record*)sb;
-  int* d_ord = (int*)(sb + ord_off);
-  int* d_cnt = (int*)(sb + cnt_off);
   hipStream_t st = nullptr;
+  Stager sg;                                // the recorder's tables: records, their callback order, two counters
+  const int i_rec = sg.add_scratch(rec_bytes), i_ord = sg.add_scratch((size_t)dev_cap * 4), i_cnt = sg.add_scratch(64);
+  RT_TRY(sg.reserve(c, st));
+  rt_ray_record* d_rec = sg.ptr<rt_ray_record>(i_rec);
+  int* d_ord = sg.ptr<int>(i_ord);
+  int* d_cnt = sg.ptr<int>(i_cnt);
   if (refr)
     hipLaunchKernelGGL((record_ray_kernel<true>), dim3(1), dim3(64), 0, st, c->dev, x, y, (int)max_depth, d_rec, d_ord, dev_cap, d_cnt);
   else

@@ -1,10 +1,15 @@
-// launch_plan.h -- every decision of a row launch as pure host code: plain C++17, no HIP header and no
-// rt_device.h, so tests/test_launch_plan.py compiles and runs it on a CPU.  Three functions:
-//   band_geometry     the row and band checks and the tile arithmetic of a band launch
+// launch_plan.h -- every decision of a launch as pure host code: plain C++17, no HIP header and no
+// rt_device.h, so tests/test_launch_plan.py compiles and runs it on a CPU.  Four functions:
+//   band_geometry     the row and band checks and the tile arithmetic of a row launch
+//   clamp_bands       the same checks (band_checks) for a side entry, and the layout cut to the rows that exist
 //   plan_row_launch   which kernel a launch runs, and what it is handed (masks, records, sky fill)
 //   order_from_costs  a calibration's tile costs -> the dispatch order and the slot's two choices
-// The callers (k_rows.hip launch_bands, k_stereo.hip launch_views, k_masks.hip, rt_ctx.hip
-// finish_calibration) see rt_device.h and pass its constants in.
+// Two band rules, because two kinds of kernel read a layout.  The row launches (k_rows.hip launch_bands, k_stereo.hip
+// launch_views, k_masks.hip) keep the caller's layout as it is -- band_geometry: their tile orders, masks and
+// records are keyed by it, and the render kernels drop the rows >= H themselves.  The side entries (k_views.hip
+// antialias_rows, k_stats.hip count_rows, k_hits.hip hits_rows) stage and copy back exactly n_rows packed rows, so
+// the host cuts the layout first -- clamp_bands: bands that start at or past H go, the last band ends at H.
+// The callers see rt_device.h and pass its constants in (rt_ctx.hip finish_calibration among them).
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -39,32 +44,56 @@
 
 namespace rt {
 
-// ---- band_geometry ------------------------------------------------------------------------------------
+// ---- band_geometry, clamp_bands ------------------------------------------------------------------------
 struct BandGeometry {
-  enum { OK = 0, NOTHING, REJECTED } status;   // NOTHING: zero rows or zero bands (launch_bands: RT_OK; the mask calls fail)
+  enum { OK = 0, NOTHING, REJECTED } status;   // NOTHING: zero rows or zero bands (the launches: RT_OK; the mask calls fail)
   char error[64];                              // not OK: the message (RT_ERR_INVALID); NOTHING: "no rows"
-  uint32_t n_rows;
+  uint32_t y_first, band_rows, band_pitch, n_rows;   // OK: the layout the kernels receive, and its 8x8 tiles
   int tiles_x, tiles_y;
   size_t n_tiles;
 };
 
-inline BandGeometry band_geometry(int width, int height, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch,
-                                  uint32_t n_bands) {
-  BandGeometry g = {};
+// The checks the two rules share, in this order; true: the layout passed them (g is not accepted yet).
+inline bool band_checks(BandGeometry& g, int height, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands) {
+  g = {};
   g.status = BandGeometry::REJECTED;
-  const uint64_t rows = (uint64_t)band_rows * n_bands;
   if (band_rows == 0 || n_bands == 0) { g.status = BandGeometry::NOTHING; snprintf(g.error, sizeof g.error, "no rows"); }
   else if (band_pitch < band_rows && n_bands > 1) snprintf(g.error, sizeof g.error, "band pitch %u < band rows %u", band_pitch, band_rows);
   else if (y_first >= (uint32_t)height) snprintf(g.error, sizeof g.error, "first row %u >= height %d", y_first, height);
-  else if (rows > (1u << 24)) snprintf(g.error, sizeof g.error, "too many rows");
-  else {
-    const int tile_h = 64 / RT_TILE_W;         // rt_device.h RT_TILE_H
-    g.status = BandGeometry::OK;
-    g.n_rows = (uint32_t)rows;
-    g.tiles_x = (width + RT_TILE_W - 1) / RT_TILE_W;
-    g.tiles_y = (int)((rows + tile_h - 1) / tile_h);
-    g.n_tiles = (size_t)g.tiles_x * (size_t)g.tiles_y;
-  }
+  else return true;
+  return false;
+}
+inline void band_accept(BandGeometry& g, int width, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_rows) {
+  const uint32_t tile_h = 64 / RT_TILE_W;      // rt_device.h RT_TILE_H
+  g.status = BandGeometry::OK;
+  g.y_first = y_first; g.band_rows = band_rows; g.band_pitch = band_pitch; g.n_rows = n_rows;
+  g.tiles_x = (width + RT_TILE_W - 1) / RT_TILE_W;
+  g.tiles_y = (int)((n_rows + tile_h - 1) / tile_h);
+  g.n_tiles = (size_t)g.tiles_x * (size_t)g.tiles_y;
+}
+
+// A row launch: the caller's layout as it is, at most 2^24 packed rows.
+inline BandGeometry band_geometry(int width, int height, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch,
+                                  uint32_t n_bands) {
+  BandGeometry g;
+  if (!band_checks(g, height, y_first, band_rows, band_pitch, n_bands)) return g;
+  const uint64_t rows = (uint64_t)band_rows * n_bands;
+  if (rows > (1u << 24)) snprintf(g.error, sizeof g.error, "too many rows");
+  else band_accept(g, width, y_first, band_rows, band_pitch, (uint32_t)rows);
+  return g;
+}
+
+// A side entry: the bands that start below H, the last of them cut to H; a single band becomes (y_first, rows, rows).
+// Every packed row r < n_rows then exists: rt_bodies.h band_row(r) < H.
+inline BandGeometry clamp_bands(int width, int height, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch,
+                                uint32_t n_bands) {
+  BandGeometry g;
+  if (!band_checks(g, height, y_first, band_rows, band_pitch, n_bands)) return g;
+  const uint32_t H = (uint32_t)height;
+  if (n_bands > 1) n_bands = std::min(n_bands, (H - 1 - y_first) / band_pitch + 1);
+  const uint32_t last_rows = std::min(band_rows, H - (y_first + (n_bands - 1) * band_pitch));
+  if (n_bands == 1) band_rows = band_pitch = last_rows;
+  band_accept(g, width, y_first, band_rows, band_pitch, (n_bands - 1) * band_rows + last_rows);
   return g;
 }
 

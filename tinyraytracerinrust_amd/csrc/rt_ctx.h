@@ -3,7 +3,8 @@
 // k_rows.hip (the row kernels' launches), k_stereo.hip (two-eye scenes' launches), k_masks.hip (tile masks and
 // dispatch records), k_wavefront.hip, k_views.hip, spec_ctx.hip.  The launches' decisions are launch_plan.h's
 // (pure host code, no HIP); this header holds what they share on the device side: the slot cache, the order
-// slots' acquisition and calibration, the end of a launch, the template dispatch.  Host code only.
+// slots' acquisition and calibration, the end of a launch, the side entries' bracket and plane stager, the
+// template dispatch.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -254,6 +255,42 @@ int finish_calibration(rt_ctx* c, hipStream_t st, rt_ctx::OrderSlot* slot, const
 // memory (the launch rendered into the context's scratch) and the wait for it.
 struct HostCopy { void* out; size_t stride; const uint8_t* src; size_t src_stride, row_bytes, n_rows; };   // out null: none
 int finish_launch(rt_ctx* c, hipStream_t st, const HostCopy& hc, bool mark);
+// The launch bracket of the side entries (k_views.hip, k_points.hip, k_stats.hip, k_hits.hip).  begin_launch: the
+// timing pair's start event; what an entry keeps out of rt_ctx_last_kernel_ms (memsets of its sums) it enqueues
+// first.  end_launch, behind the entry's last kernel: the launch error, the stop event, the completion mark.
+inline int begin_launch(rt_ctx* c, hipStream_t st) { if (c->timing) RT_HIP(hipEventRecord(c->ev0, st)); return RT_OK; }
+inline int end_launch(rt_ctx* c, hipStream_t st) { RT_HIP(hipGetLastError()); return finish_launch(c, st, HostCopy{}, true); }
+// The host-or-device planes of a side entry.  The entry registers them (add_*: the plane's index), then reserve()s:
+// every pointer is classified once, a device plane with an `align` is checked (pointer and stride), the host planes
+// and the entry's own tables get 256-aligned offsets in the context's scratch, ensure_scratch runs ONCE for the
+// total -- it may free and reallocate the buffer, so no pointer into it is formed before -- and the host inputs are
+// copied in on st.  Only then ptr() and stride() say what the kernel takes: a device plane as the caller passed it,
+// a host plane as packed rows in the scratch.  finish(): the host outputs' copies back on st, and a wait for st
+// exactly when a plane was staged or the entry reads something of its own back (must_sync).
+struct Stager {
+  // p null: a plane not asked for (ptr() null, nothing staged); a contiguous array is one row of row_bytes.
+  int add_out(void* p, size_t stride, size_t row_bytes, size_t n_rows, size_t align, const char* what) {
+    return add({p, stride, row_bytes, n_rows, align, what, OUT, true, 0});
+  }
+  int add_in(const void* p, size_t stride, size_t row_bytes, size_t n_rows, size_t align, const char* what) {
+    return add({const_cast<void*>(p), stride, row_bytes, n_rows, align, what, IN, true, 0});
+  }
+  int add_scratch(size_t bytes) { return add({nullptr, bytes, bytes, 1, 0, "", TABLE, false, 0}); }
+  int reserve(rt_ctx* c, hipStream_t st);
+  template <class T = uint8_t>
+  T* ptr(int k) const { return (T*)(pl[k].dev ? pl[k].p : base + pl[k].off); }
+  size_t stride(int k) const { return pl[k].dev ? pl[k].stride : pl[k].row_bytes; }
+  int finish(hipStream_t st, bool must_sync);
+
+ private:
+  enum Kind { OUT, IN, TABLE };
+  struct Plane { void* p; size_t stride, row_bytes, n_rows, align; const char* what; Kind kind; bool dev; size_t off; };
+  int add(const Plane& q) { pl[n] = q; return n++; }
+  Plane pl[6];                                   // the most an entry has: five (rt_antialias, rt_first_hits_points)
+  int n = 0;
+  uint8_t* base = nullptr;
+  bool staged = false;
+};
 void drop_order(rt_ctx::OrderSlot& s);         // frees an order table (hipFree waits for its readers)
 void drop_orders(rt_ctx* c);
 void reset_order_choices(rt_ctx* c);           // a same-structure upload keeps the orders; the ray-tree wavefront choice is timed again

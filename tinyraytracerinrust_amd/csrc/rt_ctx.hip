@@ -1,6 +1,7 @@
 // rt_ctx.hip -- the device context of the C ABI (include/rt_abi.h): device discovery, context
 // create / free, scene upload (rt::flatten -> one HBM blob, rt_blob.h), options, own-queue streams, and what
-// the row launches share: the order slots (acquire_order, finish_calibration) and finish_launch.
+// the row launches share: the order slots (acquire_order, finish_calibration) and finish_launch; what the side
+// entries share: the host-or-device planes' Stager (their launch bracket is two lines of rt_ctx.h).
 // Host code only; the kernels and their launches live in k_rows.hip, k_stereo.hip, k_wavefront.hip, k_views.hip.
 #include <stdio.h>
 #include <stdlib.h>
@@ -101,6 +102,40 @@ int finish_launch(rt_ctx* c, hipStream_t st, const HostCopy& hc, bool mark) {
     RT_HIP(hipMemcpy2DAsync(hc.out, hc.stride, hc.src, hc.src_stride, hc.row_bytes, hc.n_rows, hipMemcpyDeviceToHost, st));
     RT_HIP(hipStreamSynchronize(st));
   }
+  return RT_OK;
+}
+
+// rows between a caller's plane and its packed copy in the scratch: one copy where both are contiguous
+static hipError_t copy_rows(void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t row_bytes, size_t n_rows,
+                            hipMemcpyKind kind, hipStream_t st) {
+  if (n_rows == 1 || (dst_stride == row_bytes && src_stride == row_bytes)) return hipMemcpyAsync(dst, src, row_bytes * n_rows, kind, st);
+  return hipMemcpy2DAsync(dst, dst_stride, src, src_stride, row_bytes, n_rows, kind, st);
+}
+
+int Stager::reserve(rt_ctx* c, hipStream_t st) {
+  size_t total = 0;
+  for (Plane* q = pl; q < pl + n; ++q) {
+    if (q->kind != TABLE) q->dev = !q->p || is_device_ptr(q->p);
+    if (q->p && q->dev && q->align && (((uintptr_t)q->p | q->stride) & (q->align - 1)))
+      return fail(RT_ERR_INVALID, "%s rows must be %zu-byte aligned", q->what, q->align);
+    if (q->dev) continue;
+    q->off = total;
+    total = (total + q->row_bytes * q->n_rows + 255) & ~(size_t)255;
+    staged = staged || q->kind != TABLE;
+  }
+  RT_TRY(ensure_scratch(c, total));
+  base = (uint8_t*)c->scratch;
+  for (const Plane* q = pl; q < pl + n; ++q)
+    if (q->kind == IN && !q->dev)
+      RT_HIP(copy_rows(base + q->off, q->row_bytes, q->p, q->stride, q->row_bytes, q->n_rows, hipMemcpyHostToDevice, st));
+  return RT_OK;
+}
+
+int Stager::finish(hipStream_t st, bool must_sync) {
+  for (const Plane* q = pl; q < pl + n; ++q)
+    if (q->kind == OUT && !q->dev)
+      RT_HIP(copy_rows(q->p, q->stride, base + q->off, q->row_bytes, q->row_bytes, q->n_rows, hipMemcpyDeviceToHost, st));
+  if (staged || must_sync) RT_HIP(hipStreamSynchronize(st));
   return RT_OK;
 }
 

@@ -291,6 +291,25 @@ def _check_rows(a, dtype: str, what: str) -> None:
         raise ValueError(f"the rows of the {what} must be contiguous")
 
 
+def _address(a) -> Tuple[int, int]:
+    """(address, row stride in bytes) of a numpy array or a torch tensor, as the library takes a plane."""
+    if isinstance(a, np.ndarray):
+        return a.ctypes.data, a.strides[0]
+    return a.data_ptr(), a.stride(0) * a.element_size()
+
+
+def _stream_handle(stream, device=None) -> int:
+    """The stream a call runs on, as the library takes it: ``stream`` (a torch.cuda.Stream) if given; else torch's
+    current stream on ``device`` (a torch device or an index) when the call involves a device tensor; else 0, the
+    device's default stream.  Imports torch only for the current stream."""
+    if stream is not None:
+        return stream.cuda_stream
+    if device is None:
+        return 0
+    import torch
+    return torch.cuda.current_stream(device).cuda_stream
+
+
 class Renderer:
     """Owner of an ``rt_ctx*``: one device, its stream, the uploaded scene."""
 
@@ -331,9 +350,7 @@ class Renderer:
         dev = torch.device("cuda", self.device)
         if out is None:
             out = torch.empty((y1 - y0, self.width, 4), dtype=torch.float64 if f64 else torch.uint8, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        self.render_rows_into(y0, y1, out.data_ptr(), out.stride(0) * out.element_size(), max_depth,
-                              st.cuda_stream, f64)
+        self.render_rows_into(y0, y1, *_address(out), max_depth, _stream_handle(stream, dev), f64)
         return out
 
     def rows_launcher(self, y0: int, y1: int, out, max_depth: int = -1, stream=None):
@@ -360,11 +377,10 @@ class Renderer:
                          max_depth: int = -1, stream=None) -> None:
         """rt_render_row_bands into a device uint8 tensor ``out`` of >= n_bands*band_rows rows: RGBA8
         (rows, W, 4), or packed RGB8 (rows, W, 3) through rt_render_row_bands_rgb8."""
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
         fn = lib().rt_render_row_bands_rgb8 if out.shape[-1] == 3 else lib().rt_render_row_bands
-        check(fn(self.h, y_first, band_rows, band_pitch, n_bands, max_depth, ctypes.c_void_p(out.data_ptr()),
-                 out.stride(0) * out.element_size(), ctypes.c_void_p(st.cuda_stream)))
+        ptr, stride = _address(out)
+        check(fn(self.h, y_first, band_rows, band_pitch, n_bands, max_depth, ctypes.c_void_p(ptr), stride,
+                 ctypes.c_void_p(_stream_handle(stream, self.device))))
 
     def render_rows_host(self, y0: int, y1: int, max_depth: int = -1, f64: bool = False) -> np.ndarray:
         """Synchronous render into a host numpy array (the library stages through HBM)."""
@@ -386,19 +402,17 @@ class Renderer:
         array (returns numpy).  Returns (anti-aliased frame, sub-pixel rays traced); the frame is
         float64 RGBA with ``f64``."""
         rays = ctypes.c_uint64(0)
-        if isinstance(frame, np.ndarray):
+        host = isinstance(frame, np.ndarray)
+        if host:
             src = np.ascontiguousarray(frame, dtype=np.uint8)
             res = out if out is not None else np.empty(src.shape, np.float64 if f64 else np.uint8)
-            sp, ss, rp, rs = src.ctypes.data, src.strides[0], res.ctypes.data, res.strides[0]
-            st = 0
         else:
             import torch
             src = frame
             res = out if out is not None else torch.empty(tuple(frame.shape), dtype=torch.float64 if f64 else torch.uint8,
                                                           device=frame.device)
-            sp, ss = src.data_ptr(), src.stride(0) * src.element_size()
-            rp, rs = res.data_ptr(), res.stride(0) * res.element_size()
-            st = (stream if stream is not None else torch.cuda.current_stream(frame.device)).cuda_stream
+        (sp, ss), (rp, rs) = _address(src), _address(res)
+        st = 0 if host else _stream_handle(stream, frame.device)
         u8p, u8s, fp, fs = (None, 0, rp, rs) if f64 else (rp, rs, None, 0)
         check(lib().rt_antialias(self.h, ctypes.c_void_p(sp), ss, float(threshold), int(level), int(max_depth),
                                  ctypes.c_void_p(u8p), u8s, ctypes.c_void_p(fp), fs, ctypes.byref(rays),
@@ -415,19 +429,17 @@ class Renderer:
         given, needs at least that many rows); rows past the frame's height are not written."""
         rays = ctypes.c_uint64(0)
         rows = int(band_rows) * int(n_bands)
-        if isinstance(frame, np.ndarray):
+        host = isinstance(frame, np.ndarray)
+        if host:
             src = np.ascontiguousarray(frame, dtype=np.uint8)
             res = out if out is not None else np.zeros((rows, src.shape[1], 4), np.float64 if f64 else np.uint8)
-            sp, ss, rp, rs = src.ctypes.data, src.strides[0], res.ctypes.data, res.strides[0]
-            st = 0
         else:
             import torch
             src = frame
             res = out if out is not None else torch.zeros((rows, frame.shape[1], 4),
                                                           dtype=torch.float64 if f64 else torch.uint8, device=frame.device)
-            sp, ss = src.data_ptr(), src.stride(0) * src.element_size()
-            rp, rs = res.data_ptr(), res.stride(0) * res.element_size()
-            st = (stream if stream is not None else torch.cuda.current_stream(frame.device)).cuda_stream
+        (sp, ss), (rp, rs) = _address(src), _address(res)
+        st = 0 if host else _stream_handle(stream, frame.device)
         if tuple(src.shape) != (self.height, self.width, 4):
             raise ValueError(f"frame {tuple(src.shape)} is not the uploaded scene's {(self.height, self.width, 4)}")
         if res.shape[0] < rows or tuple(res.shape[1:]) != (self.width, 4):
@@ -447,17 +459,16 @@ class Renderer:
         """rt_antialias_edges: the GUI's "show edges" overlay of a whole quantised frame (torch device
         tensor or numpy array, as for ``antialias``).  Returns ((H, W, 4) uint8 overlay, marked pixels)."""
         n = ctypes.c_uint32(0)
-        if isinstance(frame, np.ndarray):
+        host = isinstance(frame, np.ndarray)
+        if host:
             src = np.ascontiguousarray(frame, dtype=np.uint8)
             res = np.empty(src.shape, np.uint8)
-            sp, ss, rp, rs = src.ctypes.data, src.strides[0], res.ctypes.data, res.strides[0]
-            st = 0
         else:
             import torch
             src = frame
             res = torch.empty(tuple(frame.shape), dtype=torch.uint8, device=frame.device)
-            sp, ss, rp, rs = src.data_ptr(), src.stride(0), res.data_ptr(), res.stride(0)
-            st = torch.cuda.current_stream(frame.device).cuda_stream
+        (sp, ss), (rp, rs) = _address(src), _address(res)
+        st = 0 if host else _stream_handle(None, frame.device)
         if tuple(src.shape) != (self.height, self.width, 4):
             raise ValueError(f"frame {tuple(src.shape)} is not the uploaded scene's {(self.height, self.width, 4)}")
         _check_rows(src, "uint8", "frame")
@@ -469,12 +480,7 @@ class Renderer:
         """The shared half of count_rays / count_rays_row_bands: ``n`` packed rows, ``geometry`` the call's
         leading arguments."""
         on_device = any(a is not None and not isinstance(a, np.ndarray) for a in (out_rows, out_pixels))
-        st = 0
-        if on_device:
-            import torch
-            st = (stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))).cuda_stream
-        elif stream is not None:
-            st = stream.cuda_stream
+        st = _stream_handle(stream, self.device if on_device else None)
         if out_rows is None and rows:
             out_rows = np.zeros((n, 4), np.uint64)
         if out_pixels is None and pixels:
@@ -490,11 +496,7 @@ class Renderer:
             # (torch's signed types of the same width serve as well: the counts are far below their sign bit)
             signed = dtype[1:]                # "uint64" -> "int64"
             _check_rows(a, signed if str(a.dtype).split(".")[-1] == signed else dtype, what)
-            if a.shape[0] == 0:
-                return None, 0
-            if isinstance(a, np.ndarray):
-                return a.ctypes.data, a.strides[0]
-            return a.data_ptr(), a.stride(0) * a.element_size()
+            return _address(a) if a.shape[0] else (None, 0)
 
         rp, rs = address(out_rows, (4,), "uint64", "row counts")
         if out_rows is not None and rs not in (0, 32):
@@ -551,12 +553,11 @@ class Renderer:
         want = {"object": True, "distance": True, "shadow": bool(shadow) or "shadow" in out,
                 "normal": bool(normal) or "normal" in out}
         made = [name for name, _, _ in self._HIT_PLANES if want[name] and out.get(name) is None]
-        st = stream.cuda_stream if stream is not None else 0
-        if made or any(a is not None and not isinstance(a, np.ndarray) for a in out.values()):
+        on_device = bool(made) or any(a is not None and not isinstance(a, np.ndarray) for a in out.values())
+        st = _stream_handle(stream, self.device if on_device else None)
+        if made:
             import torch
             dev = torch.device("cuda", self.device)
-            if stream is None:
-                st = torch.cuda.current_stream(dev).cuda_stream
         planes = _lib.rt_hit_planes()
         res = {}
         for name, dtype, tail in self._HIT_PLANES:
@@ -572,9 +573,9 @@ class Renderer:
             res[name] = a
             if a.shape[0] == 0:
                 continue
-            host = isinstance(a, np.ndarray)
-            setattr(planes, name, a.ctypes.data if host else a.data_ptr())
-            setattr(planes, name + "_stride", a.strides[0] if host else a.stride(0) * a.element_size())
+            ptr, stride = _address(a)
+            setattr(planes, name, ptr)
+            setattr(planes, name + "_stride", stride)
         if n > 0:
             check(fn(self.h, *geometry, ctypes.byref(planes), ctypes.c_void_p(st)))
         return res
