@@ -92,6 +92,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   }
   const HostCopy hc = {target == out ? nullptr : out, stride, target, tstride, row_bytes, g.n_rows};
   const int a0 = (int)y_first, a1 = (int)band_rows, a2 = (int)band_pitch, a3 = (int)g.n_rows;
+  const WfRows wf_rows = {(int)g.y_first, (int)g.band_rows, (int)g.band_pitch, (int)g.n_rows};
   // a two-eye scene (stereoscopic, anaglyph): one launch of the view megakernel over both eyes' tiles
   if (c->views.kind) return launch_views(c, st, a0, a1, a2, a3, max_depth, target, tstride, f64, rgbi, hc);
   const int32_t key[8] = {a0, a1, a2, a3, max_depth, f64 ? 1 : 0, c->dev.width, RT_CAMERA_PERSPECTIVE};
@@ -117,7 +118,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   c->last_records = plan.records;
   if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
   if (plan.path == LaunchPlan::WAVEFRONT) {
-    RT_TRY(launch_wavefront(c, st, a0, a1, a2, a3, max_depth, target, tstride, f64, rgbi, n_tiles));
+    RT_TRY(launch_wavefront(c, st, wf_rows, max_depth, target, tstride, f64, rgbi, n_tiles));
     return finish_launch(c, st, hc, true);
   }
   c->last_sky_slot = plan.sky ? rec_slot : nullptr;
@@ -180,9 +181,9 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
     // one untimed wavefront launch first: it allocates (or grows) the wavefront and pair arenas, which
     // the megakernel's timed launch had no counterpart of (a cold first launch could otherwise decide
     // the choice for the geometry)
-    RT_TRY(launch_wavefront(c, st, a0, a1, a2, a3, max_depth, target, tstride, f64, rgbi, n_tiles));
+    RT_TRY(launch_wavefront(c, st, wf_rows, max_depth, target, tstride, f64, rgbi, n_tiles));
     RT_HIP(hipEventRecord(c->tev0, st));
-    RT_TRY(launch_wavefront(c, st, a0, a1, a2, a3, max_depth, target, tstride, f64, rgbi, n_tiles));
+    RT_TRY(launch_wavefront(c, st, wf_rows, max_depth, target, tstride, f64, rgbi, n_tiles));
     RT_HIP(hipEventRecord(c->tev1, st));
     RT_HIP(hipEventSynchronize(c->tev1));
     RT_HIP(hipEventElapsedTime(&wf_ms, c->tev0, c->tev1));

@@ -1,8 +1,9 @@
 // rt_ctx.h -- the device context behind the C ABI (include/rt_abi.h: rt_ctx_*), shared by the
 // host halves of the kernel translation units: rt_ctx.hip (create / upload / options / streams),
 // k_rows.hip (the row kernels' launches), k_stereo.hip (two-eye scenes' launches), k_masks.hip (tile masks and
-// dispatch records), k_wavefront.hip, k_views.hip, spec_ctx.hip.  The launches' decisions are launch_plan.h's
-// (pure host code, no HIP); this header holds what they share on the device side: the slot cache, the order
+// dispatch records), k_wavefront.hip (the wavefront path's level kernels and its launch), k_wf_pairs.hip (its pair
+// path), k_views.hip, spec_ctx.hip.  The launches' decisions are launch_plan.h's and wf_plan.h's (pure host code,
+// no HIP); this header holds what they share on the device side: the slot cache, the order
 // slots' acquisition and calibration, the end of a launch, the side entries' bracket and plane stager, the
 // template dispatch.  Host code only.
 #pragma once
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "launch_plan.h"
+#include "wf_plan.h"
 #include "rt_blob.h"
 #include "scene.h"
 #include "spec.h"
@@ -240,6 +242,12 @@ void with_mode(int mode, F&& f) {
   else f(std::integral_constant<int, RT_MODE_REFL>{});
 }
 template <class F>
+void with_span(int span, F&& f) {   // the wavefront fold's levels per launch: 1, 2 or 3
+  if (span >= 3) f(std::integral_constant<int, 3>{});
+  else if (span == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 1>{});
+}
+template <class F>
 void with_flags(bool f64, bool cal, bool fc, F&& f) {   // f(F64, CAL, FC)
   with_bool(f64, [&](auto d) { with_bool(cal, [&](auto c) { with_bool(fc, [&](auto k) { f(d, c, k); }); }); });
 }
@@ -297,7 +305,7 @@ void reset_order_choices(rt_ctx* c);           // a same-structure upload keeps 
 // k_masks.hip: the tile-mask tables
 void drop_masks(rt_ctx* c);                    // every table (upload, free): hipFree waits for their readers
 bool masks_usable(const rt_ctx* c);            // the uploaded scene has a mask scene (LaunchFacts::masks_ok)
-// The mask table's slot of the geometry (a0..a3 as launch_wavefront) for a launch on st, filled on st first if it
+// The mask table's slot of the geometry (a0..a3: y_first, band_rows, band_pitch, n_rows) for a launch on st, filled on st first if it
 // is new since the upload
 int mask_slot(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t n_tiles, rt_ctx::MaskSlot** out);
 // The dispatch records (RecSlot) of a launch of n_entries order entries (d_order of calibration order_id; null and
@@ -316,16 +324,19 @@ int64_t record_lean_entries(rt_ctx* c, const void* rslot, uint64_t rec_id);   //
 bool record_lean_range(const void* rslot, uint32_t* first, uint32_t* end);
 uint64_t record_id(const void* rslot);
 size_t put_mask_scene(const FlatScene& f, std::vector<uint8_t>& blob, bool* ok);   // appends the RtTileMaskScene
-int ensure_scratch(rt_ctx* c, size_t bytes);   // grow-only device scratch for host-pointer launches
+// A grow-only device buffer of the context: at least `need` bytes at p.  Growing frees the old buffer first (hipFree
+// waits for the launches that read it); a failed allocation leaves p null and have 0.
+int grow_device(void*& p, size_t& have, size_t need);
+int ensure_scratch(rt_ctx* c, size_t bytes);   // the scratch for host-pointer launches, through grow_device
 bool is_device_ptr(const void* p);
 // Diagnostic switches read from the environment exist only in a diagnostic build (make diag
 // DIAG=-DRT_DIAG_ENV): RT_TILE_ORDER_DEBUG (rt_ctx.hip / k_rows.hip: tile-cost statistics and the
 // kernel each calibration picked, on stderr) and scene.cpp's flattening switches.  The product
 // reads no environment variable.
 bool diag_env(const char* name);
-// k_wavefront.hip: the wavefront path for rows (y_first, band_rows, band_pitch, n_rows) = a0..a3
-int launch_wavefront(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, int max_depth, uint8_t* target,
-                     size_t tstride, bool f64, int rgbi, size_t n_tiles, int retry = 0);
+// k_wavefront.hip: the wavefront path for the rows of a band layout (wf_plan.h plan_wavefront decides, this carries out)
+int launch_wavefront(rt_ctx* c, hipStream_t st, WfRows rows, int max_depth, uint8_t* target, size_t tstride, bool f64,
+                     int rgbi, size_t n_tiles, int retry = 0);
 // k_stereo.hip: a two-eye scene's row launch (launch_bands' arguments after its checks)
 int launch_views(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, int max_depth, uint8_t* target, size_t tstride,
                  bool f64, int rgbi, const HostCopy& hc);

@@ -139,15 +139,17 @@ int Stager::finish(hipStream_t st, bool must_sync) {
   return RT_OK;
 }
 
-int ensure_scratch(rt_ctx* c, size_t bytes) {
-  if (c->scratch_bytes >= bytes) return RT_OK;
-  if (c->scratch) (void)hipFree(c->scratch);
-  c->scratch = nullptr;
-  c->scratch_bytes = 0;
-  RT_HIP(hipMalloc(&c->scratch, bytes));
-  c->scratch_bytes = bytes;
+int grow_device(void*& p, size_t& have, size_t need) {
+  if (have >= need) return RT_OK;
+  if (p) (void)hipFree(p);                  // waits for launches that may still use it
+  p = nullptr;
+  have = 0;
+  RT_HIP(hipMalloc(&p, need));
+  have = need;
   return RT_OK;
 }
+
+int ensure_scratch(rt_ctx* c, size_t bytes) { return grow_device(c->scratch, c->scratch_bytes, bytes); }
 
 // The completion event of stream st for c (created on first use; with more than 16 streams the
 // least recently added one's launches are waited for and its event reused).  Row launches BIND it to

@@ -1,15 +1,17 @@
-// wf_sort.hip -- the wavefront path's orderings (k_wavefront.hip): the in-tree bucket sort below
+// wf_sort.hip -- the wavefront path's orderings (k_wavefront.hip, k_wf_pairs.hip): the in-tree bucket sort below
 // orders the pair path's (object, pair) lists, its hit points, and the non-pair levels' rays by the
-// top 12 bits of their coherence key.
+// top 12 bits of their coherence key.  Its bin limits and its prototype: wf_sort.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+
+#include "wf_sort.h"
 
 // ---------------------------------------------------------------------------- bucket sort
 // The pair path's sort of (object, pair) by object: few keys (the scene's objects), many items.  A
 // counting sort in three launches at most (a radix sort of a few million items takes a dozen: rocPRIM's
 // block sort + merge passes below its one-sweep size), not stable -- the pair order within an
-// object does not matter (k_wavefront.hip wfp_*: the folds are atomic min / add / or).
+// object does not matter (k_wf_pairs.hip wfp_*: the folds are atomic min / add / or).
 //   hist:    per workgroup an LDS histogram of its grid-stride share, added to cnt[] (one atomic per
 //            nonzero bin and workgroup);
 //   scan:    one workgroup turns cnt[] into exclusive offsets in place (a launch of its own: fusing it
@@ -22,8 +24,6 @@
 // its runs on a second, zeroed word per bin (cnt[RT_BS_FUSED_BINS + b]): a launch boundary costs
 // 4-6 us on the pair path's small levels (profiles/r07k_fractal_kernel_stats.csv), the scan of 2 K
 // words a fraction of one.
-#define RT_BS_MAX_BINS 4096
-#define RT_BS_FUSED_BINS 2048
 #define RT_BS_THREADS 256
 #define RT_BS_PER_THREAD 16
 __device__ __forceinline__ uint32_t rt_bs_bin(uint32_t key, int shift, uint32_t nb) {
