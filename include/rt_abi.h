@@ -452,6 +452,20 @@ int rt_ctx_synchronize(rt_ctx* ctx);
  * only non-calibrating megakernel launches that read records take them.  0: no record says lean.  Same pixels.
  * rt_ctx_kernel_info says "; lean tiles: off" or "; lean tiles: on (N entries)" ahead of "; sky fill: ..."
  * ("on (count pending)" until the table's check has completed; the call never waits).
+ * RT_OPT_TRACED_MASKS: the predicate behind the mask words holds for every ray of a tile's cone; the row kernels
+ * trace the pixel centres alone.  A traced record table is narrowed once, by a pass of the program's check kernel
+ * behind the gather (on the launch's stream, no host synchronisation) that traces each entry's own pixels with the
+ * render's functions: the prim word keeps the objects some pixel's primary ray hits (none: the entry is sky); in an
+ * entry whose hits are all on the mask plane the shadow words keep the boxed objects that occlude some pixel and
+ * the refl word the objects some reflected ray hits; and the entries in which nothing but the plane is left say
+ * lean (RT_OPT_LEAN_TILES) without the predicate's detour.  A traced table costs about four fifths of a frame once
+ * and is repaid after seven launches: 1 (default) a launch takes a traced table where RT_OPT_TILE_MASKS 1 itself
+ * would pick the masked megakernel (a measured tile order whose calibration found the launch throughput-bound,
+ * records on, a program that holds the lean kernels' check) and the upload has had eight row launches already
+ * (until then, and for a host that uploads every frame, the predicate's table); 2 every megakernel launch that
+ * reads records; 0 never.  Same
+ * pixels.  rt_ctx_kernel_info says "; traced masks: on / off" for the last launch, ahead of "; lean tiles: ...";
+ * the sky and lean counts are those of the table that was used.
  * Two-eye scenes (rt_scene_set_camera_kind) always take the view megakernels (k_stereo.hip: one launch over
  * the tiles of both eyes, mask-free walks): RT_KERNEL_DEFERRED, RT_KERNEL_WAVEFRONT and RT_OPT_TILE_MASKS have
  * no effect on them; RT_OPT_TILE_ORDER and RT_OPT_SPECIALIZE apply (rt_ctx_kernel_info says which kernel ran).
@@ -468,7 +482,7 @@ int rt_ctx_synchronize(rt_ctx* ctx);
 typedef enum rt_option {
   RT_OPT_KERNEL = 0, RT_OPT_TIMING = 1, RT_OPT_TILE_ORDER = 2, RT_OPT_FAST_CLAMP = 3, RT_OPT_WAVEFRONT_CAP = 4,
   RT_OPT_WAVEFRONT_PAIRS = 5, RT_OPT_SPECIALIZE = 6, RT_OPT_TILE_MASKS = 8, RT_OPT_SPEC_SAMPLES = 9,
-  RT_OPT_TILE_RECORDS = 10, RT_OPT_SKY_FILL = 11, RT_OPT_LEAN_TILES = 12
+  RT_OPT_TILE_RECORDS = 10, RT_OPT_SKY_FILL = 11, RT_OPT_LEAN_TILES = 12, RT_OPT_TRACED_MASKS = 13
 } rt_option;
 typedef enum rt_kernel_choice {
   RT_KERNEL_AUTO = 0, RT_KERNEL_MEGA = 1, RT_KERNEL_DEFERRED = 2, RT_KERNEL_WAVEFRONT = 3
@@ -491,6 +505,13 @@ int rt_ctx_tile_masks(rt_ctx* ctx, uint32_t y_first, uint32_t band_rows, uint32_
                       uint32_t* words, size_t cap_words, uint32_t* n_tiles);
 int rt_scene_tile_masks(const rt_scene* scene, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch,
                         uint32_t n_bands, uint32_t* words, size_t cap_words, int32_t info[4]);
+/* The dispatch records of the last row launch (RT_OPT_TILE_RECORDS; tests, debugging), as its kernels read them:
+ * 8 words per entry of the launch's tile order -- x0 (the tile's first column; the sign bit: the entry says
+ * lean), r0 (its first output row), then prim, shadow[0..3], refl (an empty prim word: the entry says sky).
+ * Waits for the table's gather (and its check or trace pass), copies min(cap_entries, entries) records and sets
+ * *n_entries to the table's entry count.  RT_ERR_INVALID when the last row launch read no records or its table
+ * has been dropped since (an upload, or eight newer tables). */
+int rt_ctx_tile_records(rt_ctx* ctx, uint32_t* words, size_t cap_entries, uint32_t* n_entries);
 /* Block until the context's specialised program (RT_OPT_SPECIALIZE) is loaded, at most timeout_ms
  * (< 0: no limit).  RT_OK: loaded, or nothing to wait for (option off, scene too large); RT_PENDING:
  * the limit passed first; a negative status: the compile failed or the guard refused it (the

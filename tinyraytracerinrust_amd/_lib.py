@@ -32,6 +32,7 @@ RT_OPT_SPEC_SAMPLES = 9
 RT_OPT_TILE_RECORDS = 10
 RT_OPT_SKY_FILL = 11
 RT_OPT_LEAN_TILES = 12
+RT_OPT_TRACED_MASKS = 13
 RT_TILEMASK_WORDS = 6     # per tile: prim, shadow[0..3], refl
 RT_KERNEL_AUTO, RT_KERNEL_MEGA, RT_KERNEL_DEFERRED, RT_KERNEL_WAVEFRONT = 0, 1, 2, 3
 RT_CAMERA_PERSPECTIVE, RT_CAMERA_STEREOSCOPIC, RT_CAMERA_ANAGLYPH = 0, 1, 2
@@ -115,6 +116,7 @@ SIGNATURES = {
     "rt_scene_sample_report": (_I, [_P, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "rt_scene_lean_report": (_I, [_P, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "rt_ctx_tile_masks": (_I, [_P, _U32, _U32, _U32, _U32, _P, ctypes.c_size_t, ctypes.POINTER(_U32)]),
+    "rt_ctx_tile_records": (_I, [_P, _P, ctypes.c_size_t, ctypes.POINTER(_U32)]),
     "rt_scene_tile_masks": (_I, [_P, _U32, _U32, _U32, _U32, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]),
     "rt_scene_spec_report": (_I, [_P, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "rt_spec_compiler_info": (_I, [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]),

@@ -62,11 +62,14 @@ __global__ __launch_bounds__(64) void tile_records_kernel(const uint32_t* __rest
 
 // The entries of a checked record table that kept the lean bit, counted as the gather counts the sky entries
 // (atomics per wave of 64 entries): out[0] their number, out[1] the maximum of ~e, out[2] the maximum of e + 1
-// (zeroed by the caller: the run [~out[1], out[2]) holds them all).
+// (zeroed by the caller: the run [~out[1], out[2]) holds them all).  n_sky (a traced table, whose pass makes sky
+// entries the gather did not count; zeroed by the caller): the entries whose prim word is empty.
 __global__ __launch_bounds__(64) void lean_count_kernel(const RtTileRec* __restrict__ recs, uint32_t n_entries,
-                                                        uint32_t* __restrict__ out) {
+                                                        uint32_t* __restrict__ out, uint32_t* __restrict__ n_sky) {
   const uint32_t e = blockIdx.x * 64u + threadIdx.x;
   const bool lean = e < n_entries && recs[e].x0 < 0;
+  const unsigned long long s = __ballot(n_sky && e < n_entries && recs[e].mask[0] == 0);
+  if ((threadIdx.x & 63) == 0 && s) atomicAdd(n_sky, (uint32_t)__popcll(s));
   const unsigned long long b = __ballot(lean);
   if ((threadIdx.x & 63) == 0 && b) {
     const uint32_t base = blockIdx.x * 64u;
@@ -371,14 +374,14 @@ bool masks_usable(const rt_ctx* c) {
 // else gathered on st, behind the mask fill: mask_slot has put the fill, or a wait for its event, on st
 // already.  Launches on other streams wait for the gather's own event.
 int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const int32_t* d_order, uint64_t order_id,
-                   uint32_t n_entries, bool lean, const RtTileRec** table, const void** rslot) {
+                   uint32_t n_entries, bool lean, bool traced, const RtTileRec** table, const void** rslot) {
   *table = nullptr;
   if (rslot) *rslot = nullptr;
   const bool sky_fill = c->sky_fill && c->sky_ok;
   bool found;
   rt_ctx::RecSlot* slot = find_slot(c->recs, [&](const rt_ctx::RecSlot& s) {
     return s.fill_id == ms->fill_id && s.order_id == order_id && s.n_entries == n_entries && s.sky_fill == sky_fill &&
-           s.lean == lean;
+           s.lean == lean && s.traced == traced;
   }, &found);
   if (!found) {
     drop_rec(*slot);
@@ -390,6 +393,7 @@ int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const 
     RT_HIP(hipHostMalloc((void**)&slot->h_sky, 4 * sizeof(uint32_t), hipHostMallocDefault));
     memset(slot->h_sky, 0, 4 * sizeof(uint32_t));
     slot->lean = lean;
+    slot->traced = traced;
     slot->rec_id = ++c->rec_ids;
     slot->sky_fill = sky_fill;
     RT_HIP(hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming));
@@ -397,20 +401,26 @@ int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const 
     slot->fill_id = ms->fill_id;
     slot->n_entries = n_entries;
     const uint32_t tiles_x = (uint32_t)((c->dev.width + RT_TILE_W - 1) / RT_TILE_W);
+    const uint32_t keep_bit = sky_fill || c->mask_plane < 0 ? 0u : 1u << c->mask_plane;   // what an empty prim word gets
     hipLaunchKernelGGL(tile_records_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, st, (const uint32_t*)ms->d_masks, d_order,
                        n_entries, (uint32_t)ms->n_tiles, tiles_x,
-                       sky_fill || c->mask_plane < 0 ? 0u : 1u << c->mask_plane, lean ? c->dev.n_lights : -1,
+                       keep_bit, lean && !traced ? c->dev.n_lights : -1,
                        c->mask_plane < 0 ? 0u : 1u << c->mask_plane, slot->d_recs, slot->d_sky);
     RT_HIP(hipGetLastError());
-    if (lean) {
+    if (lean || traced) {
       // the check (rt_bodies.h lean_check_body): the program's own kernel over every entry, behind the gather;
-      // it clears the bit where a reflected ray would hit; the entries that keep it are counted behind it
+      // it clears the bit where a reflected ray would hit; the entries that keep it are counted behind it.
+      // traced: the trace pass in its place (mode bit 0; bit 1: entries may say lean) -- the gather sets no
+      // candidate bits, the pass sets the lean bits and makes more sky entries, so the sky count is taken again
+      // with the lean count.
       const int a0 = ms->key[0], a1 = ms->key[1], a2 = ms->key[2], a3 = ms->key[3];
+      const int mode = traced ? (lean ? 3 : 1) : 0;
       RtTileRec* d_recs = slot->d_recs;
-      void* kargs[] = {&c->dev, (void*)&a0, (void*)&a1, (void*)&a2, (void*)&a3, &d_recs};
+      void* kargs[] = {&c->dev, (void*)&a0, (void*)&a1, (void*)&a2, (void*)&a3, &d_recs, (void*)&mode, (void*)&keep_bit};
       RT_HIP(hipModuleLaunchKernel(spec_fn(c, SPEC_LEAN_CHECK, false, false), n_entries, 1, 1, 64, 1, 1, 0, st, kargs, nullptr));
+      if (traced) RT_HIP(hipMemsetAsync(slot->d_sky, 0, sizeof(uint32_t), st));
       hipLaunchKernelGGL(lean_count_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, st, (const RtTileRec*)slot->d_recs, n_entries,
-                         slot->d_sky + 1);
+                         slot->d_sky + 1, traced ? slot->d_sky : (uint32_t*)nullptr);
       RT_HIP(hipGetLastError());
     }
     RT_HIP(hipMemcpyAsync(slot->h_sky, slot->d_sky, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -488,6 +498,20 @@ int rt_ctx_tile_masks(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t 
   RT_TRY(rt::mask_slot(c, nullptr, (int)y_first, (int)band_rows, (int)band_pitch, (int)g.n_rows, n_tiles, &slot));
   RT_HIP(hipStreamSynchronize(nullptr));
   RT_HIP(hipMemcpy(words, slot->d_masks, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_ctx_tile_records(rt_ctx* c, uint32_t* words, size_t cap_entries, uint32_t* n_entries) {
+  if (!c || !n_entries || (cap_entries > 0 && !words)) return fail(RT_ERR_INVALID, "null argument");
+  static_assert(sizeof(RtTileRec) == 8 * sizeof(uint32_t), "a record is 8 words");
+  const rt_ctx::RecSlot* slot = (const rt_ctx::RecSlot*)c->last_rec_slot;
+  if (!slot || !slot->valid || slot->rec_id != c->last_rec_id)
+    return fail(RT_ERR_INVALID, "the last row launch read no dispatch records (or their table has been dropped)");
+  RT_HIP(hipSetDevice(c->device));
+  RT_HIP(hipEventSynchronize(slot->ready));
+  *n_entries = slot->n_entries;
+  const size_t n = std::min(cap_entries, (size_t)slot->n_entries);
+  if (n) RT_HIP(hipMemcpy(words, slot->d_recs, n * sizeof(RtTileRec), hipMemcpyDeviceToHost));
   return RT_OK;
 }
 

@@ -61,6 +61,9 @@ LaunchFacts rt::launch_facts(const rt_ctx* c, int max_depth, bool f64, size_t n_
   f.refl_pooled = RT_LDS_POOL_REFL > 0; f.pool_byte_index = RT_POOL_OBJ_INDEX != 0;
   f.lean_tiles = c->lean_tiles;
   f.has_lean = spec_fn(c, SPEC_LEAN, f64, false) != nullptr && spec_fn(c, SPEC_LEAN_CHECK, false, false) != nullptr;
+  f.traced_masks = c->traced_masks;
+  f.has_check = spec_fn(c, SPEC_LEAN_CHECK, false, false) != nullptr;
+  f.launches_since_upload = c->launches_since_upload;
   return f;
 }
 
@@ -81,6 +84,8 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   (void)spec_poll(c);                     // the scene-specialised kernels, once their background compile is done
   c->last_masked = false;
   c->last_records = false;
+  c->last_traced = false;
+  c->last_rec_slot = nullptr;
   c->last_lean_slot = nullptr;
   // a host buffer: render into the context's scratch, copy back at the end (finish_launch)
   uint8_t* target = (uint8_t*)out;
@@ -100,6 +105,7 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   bool calibrate = false;
   if (c->kernel_opt != RT_KERNEL_WAVEFRONT) RT_TRY(acquire_order(c, key, n_tiles, st, &slot, &calibrate));   // (it takes no order)
   const LaunchPlan plan = plan_row_launch(launch_facts(c, max_depth, f64, n_tiles, slot, calibrate));
+  if (c->launches_since_upload < 0xffffffffu) ++c->launches_since_upload;
   const int32_t* order = slot && !calibrate ? slot->d_order : nullptr;
   uint32_t* cost = calibrate ? slot->d_cost : nullptr;
   const dim3 grid(order ? slot->grid : (unsigned)n_tiles);
@@ -112,10 +118,14 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   const RtTileRec* recs = nullptr;
   const void* rec_slot = nullptr;
   if (plan.masks) RT_TRY(mask_slot(c, st, a0, a1, a2, a3, n_tiles, &ms));
-  if (plan.records) RT_TRY(launch_records(c, st, ms, order, order ? slot->order_id : 0, grid.x, plan.lean, &recs, &rec_slot));
+  if (plan.records) RT_TRY(launch_records(c, st, ms, order, order ? slot->order_id : 0, grid.x, plan.lean, plan.traced, &recs,
+                                        &rec_slot));
   const uint32_t* masks = ms ? ms->d_masks : nullptr;
   c->last_masked = plan.masks;
   c->last_records = plan.records;
+  c->last_traced = plan.traced;
+  c->last_rec_slot = rec_slot;
+  c->last_rec_id = record_id(rec_slot);
   if (c->timing) RT_HIP(hipEventRecord(c->ev0, st));
   if (plan.path == LaunchPlan::WAVEFRONT) {
     RT_TRY(launch_wavefront(c, st, wf_rows, max_depth, target, tstride, f64, rgbi, n_tiles));

@@ -42,6 +42,12 @@
 // (RT_SPLIT_TILE_MASK), so launches of more tiles always take the megakernel.
 #define RT_DEFERRED_MAX_TILES 40000
 
+// RT_OPT_TRACED_MASKS 1: the row launches an upload must have had before a launch takes a traced table
+// (plan_row_launch below).
+#ifndef RT_TRACED_MIN_LAUNCHES
+#define RT_TRACED_MIN_LAUNCHES 8
+#endif
+
 namespace rt {
 
 // ---- band_geometry, clamp_bands ------------------------------------------------------------------------
@@ -131,6 +137,10 @@ struct LaunchFacts {
   bool pool_byte_index;           // RT_POOL_OBJ_INDEX
   // lean tiles: RT_OPT_LEAN_TILES, and the program holds the lean kernel for this f64 and its check
   bool lean_tiles = false, has_lean = false;
+  // traced tile masks: RT_OPT_TRACED_MASKS 0 / 1 / 2, and the program holds the pass (the check kernel: has_check)
+  int traced_masks = 0;
+  bool has_check = false;
+  uint32_t launches_since_upload = 0;   // row launches of this context since rt_ctx_upload, this one not counted
 };
 
 struct LaunchPlan {
@@ -148,6 +158,8 @@ struct LaunchPlan {
   bool defer_forced, defer_if_tail;
   // the records carry checked lean bits, and the program's lean kernel runs ahead of the megakernel
   bool lean = false;
+  // the records' words come from the trace pass (rt_bodies.h trace_masks_body), which also sets the lean bits
+  bool traced = false;
 };
 
 inline LaunchPlan plan_row_launch(const LaunchFacts& f) {
@@ -227,6 +239,17 @@ inline LaunchPlan plan_row_launch(const LaunchFacts& f) {
   // calibrating and the primary-ray kernels hold no exit for the bit, so their tables never carry it; a deferred
   // or mask-free launch reads no records at all).
   p.lean = f.lean_tiles && f.has_lean && p.path == LaunchPlan::MEGA && p.kind == SPEC_ROWS && p.records && !calibrate;
+  // Traced tile masks: a traced table costs its pass, the counts and a second gather once (4K globes: 142 + 56 +
+  // 19 us, four fifths of the 178 us frame) and gains per launch (33 us there), so it is repaid after seven
+  // launches.  RT_OPT_TRACED_MASKS 1 takes it only where RT_OPT_TILE_MASKS 1 itself would pick the masked megakernel
+  // -- a measured order whose calibration found the launch throughput-bound -- and only once the upload has been
+  // rendered RT_TRACED_MIN_LAUNCHES times (the break-even: a host that stops there has paid at most twice the
+  // cheaper choice; a host that uploads every frame, the reference's GUI, never pays); until then the launch reads
+  // the predicate's table.  2: every megakernel launch that takes records.  The words hold for the megakernel's
+  // pixels; the calibrating kernel renders every tile and the primary-ray kernel keeps the predicate's words.
+  const bool want_traced = f.traced_masks == 2 || (f.traced_masks == 1 && ordered && f.masks_pay &&
+                                                   f.launches_since_upload >= RT_TRACED_MIN_LAUNCHES);
+  p.traced = want_traced && f.has_check && p.path == LaunchPlan::MEGA && p.kind == SPEC_ROWS && p.records && !calibrate;
   // a megakernel launch without a table runs the program's mask-free megakernel (SPEC_ROWS_NOMASK)
   if (p.kind == SPEC_ROWS && !p.masks && f.has[SPEC_ROWS_NOMASK]) p.kind = SPEC_ROWS_NOMASK;
   // With the scene-specialised megakernel loaded for these launches its costliest tiles finish so

@@ -296,11 +296,130 @@ __device__ __forceinline__ void lean_body(const RtDevScene& S, int y_first, int 
   lean_pixel<FC, false>(make_ds(S), ro, rd, max_depth, &c);
   store_pixel<F64>(out + (size_t)r * stride, x, c, rgb);
 }
+// Traced tile masks (RT_OPT_TRACED_MASKS; DESIGN.md "Traced tile masks"): the predicate's words (rt_tilemask.h) hold
+// for every ray of a tile's cone, the row kernels trace the pixel centres alone.  trace_masks_body runs once per
+// record table, one wave per entry that is not sky already, traces the entry's own pixels with the functions
+// trace<false> inlines -- camera_ray_px, nearest_hit, shade_inputs, hit_inside, reflect_dir, shadow_transparency on
+// the same camera tables and the same record -- and keeps in each word only the objects whose tests accept a
+// hit for some pixel of the entry, each word ANDed with what the record held:
+//   prim       the walk runs under the record's prim word; the new word is the OR over the valid lanes of
+//              1 << oi, the plane's bit included; empty: every pixel misses, the entry is sky (keep_bit: the bit
+//              an empty word gets where no record may say sky, as the gather has it).  A walk over a subset that
+//              holds each lane's winner returns that winner: the running best is the first object in walk order
+//              that attains the minimum, and a subset keeps the relative order.
+//   An entry in which a lane hits a boxed object stops here: the kernels read its other words under all ones
+//   (trace(): plane_tile is false), so they stay the predicate's.  Else every hit is on the mask plane, and
+//   shadow[l]  for each boxed object o of the record's word the shadow walk runs under the one-bit mask 1 << o (the
+//              plane ignores masks and is always walked); bit o stays where some lane's result for that walk
+//              alone is 0.  These programs hold no transparent object (LEAN_OK), so the shadow product is
+//              any-hit, and a shadow walk culls by the segment alone, never by another object's result: the
+//              walk under the new word returns every lane what the walk under the old one did;
+//   refl       the lanes that spawn a ray (refl != 0, seen from outside) trace it under the record's refl word; the
+//              new word is the OR of 1 << oi over them, the plane's bit included (prim's argument); lanes that
+//              spawn nothing contribute nothing.
+// Lane exits mirror trace()'s, so each walk runs with the lanes it has there.  The first lane left writes the
+// words (vector stores) and the lean bit of x0 where lean_on: prim is the plane alone, no shadow word of the
+// scene's lights holds a boxed bit, refl is empty -- lean_check_body's own condition (no reflected ray accepts
+// any hit, the plane's included), reached here without its candidates' detour through the predicate.
+// Exactness is not argued from rounding: check and render call the same inlined functions on the same values, so
+// a hit point here is the render's bit for bit.  The words hold for this table's pixel centres only (a table
+// is keyed by the mask fill and the order it was gathered from, and by this option); they do not depend on
+// max_depth (a refl word is read only where a depth-1 ray exists), on the output format or on FC (no colour is
+// formed).
+template <bool FC>
+__device__ __forceinline__ void trace_masks_body(const RtDevScene& S, int y_first, int band_rows, int band_pitch, int n_rows,
+                                                 RtTileRec* __restrict__ recs, bool lean_on, uint32_t keep_bit) {
+  constexpr bool SHARE = false, OBB = true;                                // trace<false>'s walks
+  constexpr int plane = rt_spec::MASK_PLANE;
+  constexpr uint32_t plane_bit = plane >= 0 ? 1u << (plane & 31) : 0u;
+  constexpr uint32_t boxed = spec_boxed_bits<true>(0, rt_spec::N_STRAV);
+  const int lane = threadIdx.x & 63;
+  RtTileRec* const R = recs + blockIdx.x;
+  uint32_t w[RT_TILEMASK_WORDS];
+  for (int k = 0; k < RT_TILEMASK_WORDS; ++k) w[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)R->mask[k]);
+  const int x0 = __builtin_amdgcn_readfirstlane(R->x0) & 0x7fffffff, r0 = __builtin_amdgcn_readfirstlane(R->r0);
+  if (w[0] == 0) return;                                                   // sky already
+  const int x = x0 + lane % RT_TILE_W, r = r0 + lane / RT_TILE_W;
+  if (x >= S.width || r >= n_rows) return;
+  const int y = band_row(r, y_first, band_rows, band_pitch, n_rows);
+  if (y >= S.height) return;                                               // (an entry without a pixel keeps its record)
+  // the words and x0 as the first lane still here writes them; every operand is wave-uniform
+  auto put = [&](uint32_t prim, bool rest, uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3, uint32_t refl) RT_INL {
+    if (lane != (int)__builtin_ctzll(__ballot(true))) return;
+    R->mask[0] = prim;
+    if (!rest) return;
+    const uint32_t s[4] = {s0, s1, s2, s3};
+    bool lean = lean_on && prim == plane_bit && refl == 0;
+    for (int l = 0; l < 4; ++l) {
+      R->mask[1 + l] = s[l];
+      if (l < rt_spec::N_LIGHTS) lean = lean && (s[l] & boxed) == 0;
+    }
+    R->mask[5] = refl;
+    R->x0 = lean ? x0 | (int32_t)0x80000000u : x0;
+  };
+  V3 ro, rd;
+  camera_ray_px(S, x, y, &ro, &rd);
+  const DS ds = make_ds(S);
+  double t_hit;
+  const int oi = nearest_hit<SHARE, OBB>(ds, ro, rd, &t_hit, w[0]);
+  uint32_t prim = 0;
+  for (int o = 0; o < rt_spec::N_OBJECTS && o < 32; ++o)
+    if (__ballot(oi == o) != 0) prim |= 1u << o;
+  prim &= w[0];
+  if (prim == 0) prim = keep_bit;
+  if (__ballot(oi >= 0 && oi != plane) != 0 || __ballot(oi >= 0) == 0) {    // a boxed object's pixel, or sky: prim alone
+    put(prim, false, 0u, 0u, 0u, 0u, 0u);
+    return;
+  }
+  if (oi < 0) return;                                                      // a lane that missed takes no part in what follows
+  const V3 p = add(ro, scale(rd, t_hit));
+  uint32_t sh[4] = {w[1], w[2], w[3], w[4]};
+  _Pragma("unroll 1") for (int k = 0; k < rt_spec::N_LIGHTS && k < 4; ++k) {
+    RT_REC(lt, ds, lights, LIGHTS, k);                                     // RT_HIT_LIGHTS' shadow ray: the same operations
+    const V3 lv = sub(ld3(lt->p), p);
+    double ll, ill;
+    len_inv(lv, &ll, &ill);
+    const V3 sdir = scale(lv, ill);
+    const int ks = __builtin_amdgcn_readfirstlane(k);
+    const uint32_t wk = ks == 0 ? w[1] : ks == 1 ? w[2] : ks == 2 ? w[3] : w[4];
+    uint32_t todo = wk & boxed, occ = 0;
+    _Pragma("unroll 1") while (todo != 0) {
+      const uint32_t bit = (uint32_t)__builtin_amdgcn_readfirstlane((int)(todo & (0u - todo)));
+      todo ^= bit;
+      if (__ballot(shadow_transparency<SHARE, OBB>(ds, p, sdir, ll, bit) == 0.0) != 0) occ |= bit;
+    }
+    const uint32_t nw = wk & (~boxed | occ);
+    if (ks == 0) sh[0] = nw; else if (ks == 1) sh[1] = nw; else if (ks == 2) sh[2] = nw; else sh[3] = nw;
+  }
+  V3 nrm = {0.0, 0.0, 0.0};
+  Col c = {0.0, 0.0, 0.0};
+  double transp = 0.0, refl = 0.0, nlen = 0.0;
+  shade_inputs(ds, oi, p, &nrm, &c, &transp, &refl, &nlen);
+  // trace<false> at depth 0 (max_depth > 0): a reflection where rp = refl != 0 and the hit is seen from outside
+  const bool spawn = refl != 0.0 && !hit_inside(rd, nrm, nlen);
+  if (__ballot(spawn) == 0) {
+    put(prim, true, sh[0], sh[1], sh[2], sh[3], 0u);
+    return;
+  }
+  if (!spawn) return;
+  double t1;
+  const int o1 = nearest_hit<SHARE, OBB>(ds, p, reflect_dir(rd, nrm), &t1, w[5]);
+  uint32_t rw = 0;
+  for (int o = 0; o < rt_spec::N_OBJECTS && o < 32; ++o)
+    if (__ballot(o1 == o) != 0) rw |= 1u << o;
+  put(prim, true, sh[0], sh[1], sh[2], sh[3], rw & w[5]);
+}
 // The check (k_masks.hip launch_records, behind the gather and ahead of the table's `ready` event): one wave
 // per entry; a candidate entry in which any valid pixel's reflected ray hits loses its bit.
+// mode (wave-uniform): 0 the check; bit 0 the trace pass above in its place (one kernel: each kernel more costs
+// a program 7-9 s of cold compile), bit 1 with it: the table's launches run the lean kernel, entries may say lean.
 template <bool FC>
 __device__ __forceinline__ void lean_check_body(const RtDevScene& S, int y_first, int band_rows, int band_pitch, int n_rows,
-                                                RtTileRec* __restrict__ recs) {
+                                                RtTileRec* __restrict__ recs, int mode = 0, uint32_t keep_bit = 0u) {
+  if (__builtin_amdgcn_readfirstlane(mode) != 0) {
+    trace_masks_body<FC>(S, y_first, band_rows, band_pitch, n_rows, recs, (mode & 2) != 0, keep_bit);
+    return;
+  }
   const int lane = threadIdx.x & 63;
   const int x0 = recs[blockIdx.x].x0, r0 = recs[blockIdx.x].r0;
   if (__builtin_amdgcn_readfirstlane(x0) >= 0) return;

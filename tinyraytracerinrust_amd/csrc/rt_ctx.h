@@ -118,6 +118,7 @@ struct rt_ctx {
     bool lean = false;                // gathered with the lean bits and checked (RT_OPT_LEAN_TILES); the entries that
                                       //   kept theirs follow the sky count: d_sky / h_sky [1] their number, [2] ~first
                                       //   entry, [3] last entry + 1 (both 0: none)
+    bool traced = false;              // its words and lean bits are the trace pass's (RT_OPT_TRACED_MASKS)
     uint32_t n_entries = 0;           // order entries = records
     uint64_t last_use = 0;
     hipStream_t fill_stream = nullptr;
@@ -144,7 +145,16 @@ struct rt_ctx {
   bool lean_tiles = true;
   const void* last_lean_slot = nullptr;
   uint64_t last_lean_id = 0;
-  int tile_masks = 1;                   // rt_ctx_set_option(RT_OPT_TILE_MASKS): 0 never, 1 where they pay (OrderSlot::masks_pay), 2 always
+  // Traced tile masks (rt_ctx_set_option(RT_OPT_TRACED_MASKS), rt_bodies.h trace_masks_body): 0 never, 1 where the
+  // masked megakernel runs by the library's own choice (LaunchPlan::traced), 2 every megakernel launch with records.
+  // last_traced: the last row launch's table was traced; last_rec_*: that table, whatever it holds
+  // (rt_ctx_tile_records).
+  int traced_masks = 1;
+  uint32_t launches_since_upload = 0;   // row launches since rt_ctx_upload (value 1 waits for RT_TRACED_MIN_LAUNCHES)
+  bool last_traced = false;
+  const void* last_rec_slot = nullptr;
+  uint64_t last_rec_id = 0;
+  int tile_masks = 1;                  // rt_ctx_set_option(RT_OPT_TILE_MASKS): 0 never, 1 where they pay (OrderSlot::masks_pay), 2 always
   bool masks_ok = false;                // the uploaded scene has a mask scene in its blob (<= 32 objects)
   const void* d_mask_scene = nullptr;   // RtTileMaskScene in the blob
   bool last_masked = false;             // the last row launch passed a mask table (rt_ctx_kernel_info)
@@ -312,8 +322,11 @@ int mask_slot(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t 
 // 0: the identity) whose mask table is ms's, gathered on st first if the masks or the order are new.
 // lean: with the lean bits (RT_OPT_LEAN_TILES), set by the gather and cleared again by the program's check kernel
 // where a tile fails it, both on st ahead of the table's event; the context holds that kernel (LaunchPlan::lean).
+// traced: the same kernel's trace pass instead (RT_OPT_TRACED_MASKS, LaunchPlan::traced): it narrows every entry's
+// words to what its pixels' rays hit and sets the lean bits itself (lean: entries may say lean); the sky and lean
+// counts are taken behind it.
 int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const int32_t* d_order, uint64_t order_id,
-                   uint32_t n_entries, bool lean, const RtTileRec** table, const void** rslot = nullptr);
+                   uint32_t n_entries, bool lean, bool traced, const RtTileRec** table, const void** rslot = nullptr);
 void drop_records(rt_ctx* c);                  // every record table (upload, free)
 // How many of a record table's entries say sky (rslot as launch_records gave it, rec_id its RecSlot::rec_id);
 // -1: the table has been dropped since, -2: its gather has not completed yet.  Never waits.

@@ -330,6 +330,9 @@ int rt_ctx_upload(rt_ctx* c, const rt_scene* s) {
   c->mask_plane = rt::tilemask_plane(f);
   c->last_sky_slot = nullptr;
   c->last_lean_slot = nullptr;
+  c->last_rec_slot = nullptr;
+  c->last_traced = false;
+  c->launches_since_upload = 0;
   d.n_objects = (int32_t)f.objects.size();
   d.n_lights = (int32_t)f.lights.size();
   d.n_leaves = (int32_t)f.leaves.size();
@@ -408,6 +411,9 @@ int rt_ctx_kernel_info(rt_ctx* c, char* buf, size_t cap) {
   // sky fill: the last launch's records could say sky; the counts come from a pinned word once the records'
   // gather has completed (no wait: "counts pending" until then, no counts once the table has been dropped).
   // (Ahead of "last launch": callers match the text from there to the end.)
+  // traced masks: the last launch's record table went through the trace pass (ahead of "lean tiles": callers
+  // match "; lean tiles: ...; sky fill: ...; last launch:" as one run of text)
+  s += c->last_traced ? "; traced masks: on" : "; traced masks: off";
   const int64_t n_lean = c->last_lean_slot ? rt::record_lean_entries(c, c->last_lean_slot, c->last_lean_id) : -1;
   s += !c->last_lean_slot ? "; lean tiles: off" + (c->lean_tiles ? rt::spec_lean_note(c) : std::string())
        : n_lean >= 0      ? "; lean tiles: on (" + std::to_string(n_lean) + " entries)"
@@ -502,6 +508,11 @@ int rt_ctx_set_option(rt_ctx* c, int32_t option, int32_t value) {
   if (option == RT_OPT_LEAN_TILES) {
     if (value != 0 && value != 1) return fail(RT_ERR_INVALID, "RT_OPT_LEAN_TILES value %d", value);
     c->lean_tiles = value != 0;          // record tables are keyed by it: the next launch gathers its own
+    return RT_OK;
+  }
+  if (option == RT_OPT_TRACED_MASKS) {
+    if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "RT_OPT_TRACED_MASKS value %d", value);
+    c->traced_masks = value;             // record tables are keyed by what a launch takes: the next one gathers its own
     return RT_OK;
   }
   if (option == RT_OPT_WAVEFRONT_PAIRS) {

@@ -52,7 +52,7 @@ struct SpecKindRow {
   bool frames;          // declares the LDS frames (rows_lds_doubles of the mode and layout)
   bool masks;           // takes the mask operand, and RT_REC_PARAMS in a reflection-only program
   bool no_tile_masks;   // its program is prefixed with RT_TILE_MASKS 0
-  enum { WAVES_MODE, WAVES_PRIMARY, WAVES_DEFERRED, WAVES_LEAN } waves;   // where amdgpu_waves_per_eu comes from
+  enum { WAVES_MODE, WAVES_PRIMARY, WAVES_DEFERRED, WAVES_LEAN, WAVES_CHECK } waves;   // where amdgpu_waves_per_eu comes from
   bool variants;        // [f64][cal] instantiations (level 2: all four; level 1: the product's one)
   enum { ONE_EYE, REFLECTION, CONTEXT_REFLECTION, TWO_EYES, SAMPLE, LEAN } held;   // which programs hold it (spec_kernels)
   SpecBound bound;      // SPEC_BOUND_ROWS: by the mode (ray trees: SPEC_BOUND_TREE)

@@ -217,6 +217,12 @@ std::string spec_frame_layout() {
 #ifndef RT_SPEC_WAVES_LEAN
 #define RT_SPEC_WAVES_LEAN 8
 #endif
+// Their check kernel also holds the trace pass (rt_bodies.h trace_masks_body: two nearest-hit walks, a shadow walk
+// and the shading inputs live across them): at the lean kernel's 8 waves (64 VGPRs) it spilled 99 VGPRs, so it
+// takes the megakernel's 4.  It runs once per record table.
+#ifndef RT_SPEC_WAVES_CHECK
+#define RT_SPEC_WAVES_CHECK 4
+#endif
 
 // The catalogue: one row per SpecKind (spec.h SpecKindRow), the generic kernels' exact bodies.  The row kernels
 // share the generic kernels' parameters; the megakernel and the primary-ray kernel also take the launch
@@ -256,14 +262,15 @@ const SpecKindRow spec_kinds[SPEC_KINDS] = {
                    "", "aa_trace_body", "$M, $X, $L", "S, edges, req, n, size, col, max_depth, $S", true, false, true,
                    K::WAVES_MODE, false, K::SAMPLE, SPEC_BOUND_ROWS, "aa trace", "aa trace (specialised)"},
     // the lean kernel takes the megakernel's operands (one argument list serves both launches), the check the
-    // launch geometry and the record table it edits
+    // launch geometry, the record table it edits and its mode (the check, or the trace pass of RT_OPT_TRACED_MASKS)
     /* SPEC_LEAN */ {"rt_spec_lean_%d", "RtDevScene S, " ROW_PARAMS, "", "lean_body", "$F, $X",
                      "S, y_first, band_rows, band_pitch, n_rows, max_depth, out, stride, rgb$R", false, true, false,
                      K::WAVES_LEAN, true, K::LEAN, SPEC_BOUND_ROWS, nullptr, nullptr, true},
     /* SPEC_LEAN_CHECK */ {"rt_spec_lean_check",
-                           "RtDevScene S, int y_first, int band_rows, int band_pitch, int n_rows, RtTileRec* __restrict__ recs",
-                           "", "lean_check_body", "$X", "S, y_first, band_rows, band_pitch, n_rows, recs", false, false,
-                           false, K::WAVES_LEAN, false, K::LEAN, SPEC_BOUND_ROWS, nullptr, nullptr},
+                           "RtDevScene S, int y_first, int band_rows, int band_pitch, int n_rows, RtTileRec* __restrict__ recs, "
+                           "int mode, uint32_t keep_bit",
+                           "", "lean_check_body", "$X", "S, y_first, band_rows, band_pitch, n_rows, recs, mode, keep_bit", false, false,
+                           false, K::WAVES_CHECK, false, K::LEAN, SPEC_BOUND_ROWS, nullptr, nullptr},
 };
 
 // s with every $-placeholder of the catalogue replaced (vars: pairs of letter and text).
@@ -290,6 +297,7 @@ std::string spec_kernel(const SpecProgram& p, const SpecKernel& k) {
   const std::string waves = row.waves == K::WAVES_DEFERRED  ? "RT_WAVES_PER_EU_DEFERRED"
                             : row.waves == K::WAVES_PRIMARY ? std::to_string(RT_SPEC_WAVES_PRIM)
                             : row.waves == K::WAVES_LEAN    ? std::to_string(RT_SPEC_WAVES_LEAN)
+                            : row.waves == K::WAVES_CHECK   ? std::to_string(RT_SPEC_WAVES_CHECK)
                                                             : std::to_string(p.mode == RT_MODE_CHAIN ? RT_SPEC_WAVES_CHAIN : RT_SPEC_WAVES);
   std::string s = "extern \"C\" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(" + waves + "))) void " +
                   spec_kernel_name(k) + "(" + row.params;

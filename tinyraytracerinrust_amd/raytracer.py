@@ -701,6 +701,22 @@ class Renderer:
         alone are rendered by the program's lean kernel ahead of the megakernel (default on).  Same pixels."""
         check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_LEAN_TILES, 1 if on else 0))
 
+    def set_traced_masks(self, mode: int) -> None:
+        """rt_ctx_set_option(RT_OPT_TRACED_MASKS): a record table's words narrowed once to what its entries' own
+        pixels hit, by a trace pass behind the gather (same pixels): 0 never, 1 (the default) where the library
+        itself picks the masked megakernel and the upload has had eight row launches, 2 for every megakernel
+        launch that reads records."""
+        check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_TRACED_MASKS, int(mode)))
+
+    def tile_records(self) -> np.ndarray:
+        """rt_ctx_tile_records: the dispatch records of the last row launch as its kernels read them, uint32
+        [entries, 8]: x0 (sign bit: the entry says lean), r0, prim, shadow[0..3], refl."""
+        n = ctypes.c_uint32()
+        check(lib().rt_ctx_tile_records(self.h, None, 0, ctypes.byref(n)))
+        recs = np.zeros((n.value, 8), dtype=np.uint32)
+        check(lib().rt_ctx_tile_records(self.h, ctypes.c_void_p(recs.ctypes.data), n.value, ctypes.byref(n)))
+        return recs
+
     def tile_masks(self, y_first: int = 0, band_rows: Optional[int] = None, band_pitch: Optional[int] = None,
                    n_bands: int = 1) -> np.ndarray:
         """rt_ctx_tile_masks: the uploaded scene's mask table of a band launch (default: the whole frame)

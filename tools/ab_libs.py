@@ -6,7 +6,8 @@ usage: python tools/ab_libs.py LIB [LIB ...] [--config sphere1080d0|globes1080d5
        [--masks=-1,1,0]   per library: RT_OPT_TILE_MASKS (-1: leave it, for libraries without the option)
        [--records=-1,1,0] per library: RT_OPT_TILE_RECORDS (-1: leave it)
        [--sky=-1,1,0]     per library: RT_OPT_SKY_FILL (-1: leave it)
-       [--lean=-1,1,0]    per library: RT_OPT_LEAN_TILES (-1: leave it)"""
+       [--lean=-1,1,0]    per library: RT_OPT_LEAN_TILES (-1: leave it)
+       [--traced=-1,1,0,2] per library: RT_OPT_TRACED_MASKS (-1: leave it, for libraries without the option)"""
 import argparse
 import ctypes
 import os
@@ -36,6 +37,7 @@ def main():
     ap.add_argument("--records", default="", help="per library (in order): RT_OPT_TILE_RECORDS, -1 = leave the default")
     ap.add_argument("--sky", default="", help="per library (in order): RT_OPT_SKY_FILL, -1 = leave the default")
     ap.add_argument("--lean", default="", help="per library (in order): RT_OPT_LEAN_TILES, -1 = leave the default")
+    ap.add_argument("--traced", default="", help="per library (in order): RT_OPT_TRACED_MASKS, -1 = leave the default")
     a = ap.parse_args()
     import torch
     scene, W, H, depth = CONFIGS[a.config]
@@ -46,7 +48,8 @@ def main():
     records = [int(v) for v in a.records.split(",")] if a.records else [-1] * len(a.libs)
     sky = [int(v) for v in a.sky.split(",")] if a.sky else [-1] * len(a.libs)
     lean = [int(v) for v in a.lean.split(",")] if a.lean else [-1] * len(a.libs)
-    for path, level, mask, rec, sk, le in zip(a.libs, levels, masks, records, sky, lean):
+    traced = [int(v) for v in a.traced.split(",")] if a.traced else [-1] * len(a.libs)
+    for path, level, mask, rec, sk, le, tr in zip(a.libs, levels, masks, records, sky, lean, traced):
         L = ctypes.CDLL(os.path.abspath(path), mode=os.RTLD_LOCAL)
         L.rt_ctx_spec_wait.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         sc, cx = ctypes.c_void_p(), ctypes.c_void_p()
@@ -61,6 +64,8 @@ def main():
             assert L.rt_ctx_set_option(cx, 11, sk) == 0               # RT_OPT_SKY_FILL
         if le >= 0:
             assert L.rt_ctx_set_option(cx, 12, le) == 0               # RT_OPT_LEAN_TILES
+        if tr >= 0:
+            assert L.rt_ctx_set_option(cx, 13, tr) == 0               # RT_OPT_TRACED_MASKS
         assert L.rt_ctx_upload(cx, sc) == 0
         assert L.rt_ctx_spec_wait(cx, -1) == 0
         assert L.rt_ctx_set_option(cx, 1, 0) == 0                  # RT_OPT_TIMING off, as bench.py
@@ -101,10 +106,10 @@ def main():
         if not a.no_check and not torch.equal(outs[i], outs[0]):
             raise SystemExit(f"{a.libs[i]}: frame differs from {a.libs[0]}'s")
     print(f"{a.config} ({'generic' if a.generic else 'specialised'}), {n} frames per measurement, ms per frame, median of {a.rounds}:")
-    for path, level, mask, rec, sk, le, v in zip(a.libs, levels, masks, records, sky, lean, res):
+    for path, level, mask, rec, sk, le, tr, v in zip(a.libs, levels, masks, records, sky, lean, traced, res):
         w = sorted(v)
         print(f"  {w[len(w) // 2]:.4f}  ({' '.join(f'{x:.4f}' for x in v)})  {path} (RT_OPT_SPECIALIZE {level}"
-              f"{'' if mask < 0 else f', RT_OPT_TILE_MASKS {mask}'}{'' if rec < 0 else f', RT_OPT_TILE_RECORDS {rec}'}{'' if sk < 0 else f', RT_OPT_SKY_FILL {sk}'}{'' if le < 0 else f', RT_OPT_LEAN_TILES {le}'})", flush=True)
+              f"{'' if mask < 0 else f', RT_OPT_TILE_MASKS {mask}'}{'' if rec < 0 else f', RT_OPT_TILE_RECORDS {rec}'}{'' if sk < 0 else f', RT_OPT_SKY_FILL {sk}'}{'' if le < 0 else f', RT_OPT_LEAN_TILES {le}'}{'' if tr < 0 else f', RT_OPT_TRACED_MASKS {tr}'})", flush=True)
 
 
 if __name__ == "__main__":

@@ -3,6 +3,10 @@
 # FP64, issue counters), one rocprofv3 --pmc run per counter group (rocprofv3 does not split passes).
 # Afterwards, in the build container: python3 tools/pmc_summary.py ${TAG}_<config> <config> <kernel>
 # for each config (profiles/pmc_summary.json, which bench.py's roofline blocks read).
+# (globes4k: bench.py's settle phase renders far more than the RT_TRACED_MIN_LAUNCHES frames after which the default
+# takes the traced record table, so all but the first eight dispatches of the two product kernels run on it; the
+# set-up kernels -- mask fill, gathers, the lean check and the trace pass, the counts -- are dispatched once each and
+# pmc_summary.py lists them under "setup_kernels".)
 # usage (GPU box): TAG=r09z bash tools/gpu_pmc_all.sh [CONFIGS...]
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"

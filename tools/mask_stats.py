@@ -2,7 +2,8 @@
 host (rt_scene_tile_masks, no GPU): per config the share of walks whose word holds no boxed object, the boxed
 bits set per walk, and the same per class.  A walk is a tile's primary walk, and on a floor tile (its shadow
 words were computed) one shadow walk per light and the reflection walk.  RT_LIB_PATH picks another build.
-usage: python tools/mask_stats.py [globes4k globes1080 ...]"""
+usage: python tools/mask_stats.py [--truth] [globes4k globes1080 ...]
+--truth: the predicate's classes against the pixel centres' own rays in the CPU oracle (minutes per 4K frame)."""
 import os
 import sys
 
@@ -46,6 +47,63 @@ def stats(name):
         print(f"  shadow[{l}] per object, % of floor tiles: " + " ".join(f"{p:.0f}" for p in per))
 
 
+def truth(name):
+    """--truth: the predicate's classes against what the pixel centres' own rays do, from the CPU oracle alone
+    (orc_hit_signature per pixel: the object hit and the occluded lights; record_rays on floor pixels: the depth-1
+    ray's hit) -- the bound on what a table traced per entry (RT_OPT_TRACED_MASKS) can reclassify."""
+    import tinyraytracerinrust_amd as T
+    from oracle import oracle as O
+    scene, W, H = CONFIGS[name]
+    text = open(os.path.join(S, scene + ".scene")).read()
+    O.register_texture_file("worldmap.png", os.path.join(S, "worldmap.png"))
+    sc = T.Scene.compile(text, 0.0, W, H, asset_dir=S)
+    words, info = sc.tile_masks()
+    boxed, plane = np.uint32(info["boxed"]), info["plane"]
+    orc = O.OracleScene(text, 0.0, W, H, max_depth=2)
+    n_lights = min(orc.n_lights, 4)
+    tx, ty = (W + 7) // 8, (H + 7) // 8
+    obj = np.zeros(tx * ty, bool)                    # the tile holds a pixel on a boxed object
+    hit = np.zeros(tx * ty, bool)                    # ... a pixel that hits anything
+    occl = np.zeros((n_lights, tx * ty), bool)       # ... a floor pixel whose light l is occluded
+    refl = np.zeros(tx * ty, bool)                   # ... a floor pixel whose depth-1 ray hits
+    for y in range(H):
+        for x in range(W):
+            sig = orc.hit_signature(x, y)
+            if sig < 0:
+                continue
+            t = (y // 8) * tx + x // 8
+            hit[t] = True
+            if sig % 4096 - 1 != plane:
+                obj[t] = True
+                continue
+            for l in range(n_lights):
+                if (sig // 4096 >> l) & 1:
+                    occl[l, t] = True
+            if not refl[t]:
+                r = orc.record_rays(x, y, cap=4)[0].view(T.RAY_RECORD_DTYPE)
+                refl[t] = bool(((r["depth"] == 1) & (r["intersected"] != 0)).any())
+    floor_t = hit & ~obj                             # every hit of the tile is on the floor
+    p_sky = words[:, 0] == 0
+    p_prim = (words[:, 0] & boxed) != 0
+    p_floor = ~p_sky & ~p_prim
+    print(f"{name} --truth: {tx * ty} tiles; class: predicate | oracle, pixel centres")
+    print(f"  sky tiles: {p_sky.sum()} | {(~hit).sum()} (every primary ray misses)")
+    print(f"  tiles with a boxed bit in prim: {p_prim.sum()} | {obj.sum()} hold an object pixel; of the predicate's "
+          f"{(p_prim & floor_t).sum()} are all floor, {(p_prim & ~hit).sum()} all sky")
+    for l in range(n_lights):
+        p_sh = p_floor & ((words[:, 1 + l] & boxed) != 0)
+        print(f"  floor tiles with a boxed bit in shadow[{l}]: {p_sh.sum()} | {(floor_t & occl[l]).sum()} all-floor tiles have an "
+              f"occluded pixel; the word is set with no occluded pixel on {(p_sh & floor_t & ~occl[l]).sum()} all-floor tiles")
+    p_lean = p_floor & ((words[:, 5] & boxed) == 0)
+    for l in range(n_lights):
+        p_lean &= (words[:, 1 + l] & boxed) == 0
+    unshadowed = floor_t & ~occl.any(axis=0)
+    print(f"  lean tiles (predicate candidates): {p_lean.sum()} | {(unshadowed & ~refl).sum()} are all floor, unshadowed and no "
+          f"depth-1 ray hits; {unshadowed.sum()} are all floor and unshadowed, {(unshadowed & ((words[:, 5] & boxed) != 0)).sum()} of "
+          f"those have a boxed bit in refl")
+
+
 if __name__ == "__main__":
-    for n in sys.argv[1:] or ["globes4k", "globes1080"]:
-        stats(n)
+    args = [a for a in sys.argv[1:] if a != "--truth"]
+    for n in args or ["globes4k", "globes1080"]:
+        (truth if "--truth" in sys.argv[1:] else stats)(n)

@@ -48,6 +48,16 @@ def main(tag="r01", config="globes4k", kernel="render_rows_kernel"):
         for r in csv.DictReader(open(f)):
             if _is_render(r["Kernel_Name"], kernel):
                 agg[r["Kernel_Name"]][r["Counter_Name"]].append(float(r["Counter_Value"]))
+    # the kernels that set a masked launch's tables up, once per table and outside the frame's timing pair: the mask
+    # fill, the gather, the program's check kernel (the lean check, or the trace pass of RT_OPT_TRACED_MASKS in its
+    # place: one dispatch each where a context renders on the predicate's table first and the traced one after) and
+    # the lean / sky counts -- reported per dispatch under "setup_kernels", never summed into the launch
+    setup = defaultdict(lambda: defaultdict(list))
+    for f in glob.glob(os.path.join(out, f"{tag}_pmc_*", "run_counter_collection.csv")):
+        for r in csv.DictReader(open(f)):
+            m = re.search(r"(tile_masks_kernel|tile_records_kernel|lean_count_kernel|rt_spec_lean_check)", r["Kernel_Name"])
+            if m:
+                setup[m.group(1)][r["Counter_Name"]].append((int(r["Dispatch_Id"]), float(r["Counter_Value"])))
     names = set(agg)
     per_kernel = {n: {k: sum(v) / len(v) for k, v in c.items()} for n, c in agg.items()}
     # a launch's counters: the sum over its kernels (they run one after the other; every counter here is additive)
@@ -60,6 +70,8 @@ def main(tag="r01", config="globes4k", kernel="render_rows_kernel"):
            "mean": mean}
     if len(per_kernel) > 1:
         res["per_kernel"] = per_kernel
+    if setup:
+        res["setup_kernels"] = {n: {k: [v for _, v in sorted(vals)] for k, vals in c.items()} for n, c in setup.items()}
     if "FETCH_SIZE" in mean and "WRITE_SIZE" in mean:
         res["hbm_bytes_per_launch"] = int((2 * mean["FETCH_SIZE"] + mean["WRITE_SIZE"]) * 1024)
     f64 = [mean.get(k) for k in ("SQ_INSTS_VALU_ADD_F64", "SQ_INSTS_VALU_MUL_F64", "SQ_INSTS_VALU_FMA_F64")]
