@@ -235,6 +235,39 @@ int rt_trace_pixel_f64(const rt_scene* scene, double x, double y, int32_t max_de
  * synchronous.  Not a throughput path. */
 int rt_record_rays(rt_ctx* ctx, double x, double y, int32_t max_depth, rt_ray_record* records, int32_t cap,
                    int32_t* n_rays, double* rgba);
+/* The same recording for MANY samples in one launch (RayDebugger::record_rays, ray_debugger.rs:92-137, for every
+ * sample of a scanline, a dragged region or a frame; one RayDebuggerCallback call, raytracer.rs:17-19, per record):
+ * one GPU lane per sample, every sample's records packed into a segment of exactly its size, no per-sample host
+ * call.  Two stages, for perspective scenes (two-eye scenes: RT_ERR_UNSUPPORTED, as rt_record_rays); xy = n pairs
+ * of doubles as rt_render_points_f64 (fractional positions allowed); max_depth < 0: the scene's, > 16:
+ * RT_ERR_UNSUPPORTED; n > 2^26: RT_ERR_UNSUPPORTED; no scene uploaded: RT_ERR_INVALID.  xy, offsets, records and
+ * rgba_f64 are each a device or a host pointer of its own (a host array is staged in the context's scratch; device
+ * arrays are aligned to their element, device records to 16 bytes).
+ * Stage 1, rt_ray_paths_offsets: how many rays each sample's get_pixel(x, y) traces -- primary + reflect + refract,
+ * the records record_rays would push (ray_debugger.rs:101-134) -- as an exclusive prefix sum: offsets[i] = the rays
+ * of the samples before i, offsets[n] = all of them; *total (host, may be NULL) = offsets[n].  One counting kernel
+ * and a three-step scan in which no workgroup waits for another.  n == 0: RT_OK, offsets[0] = 0, *total = 0.
+ * Asynchronous on `stream` when offsets is a device pointer and total is NULL; filling total synchronises the host
+ * with `stream`, as rt_count_rays' totals does.
+ * Stage 2, rt_ray_paths: the records.  Sample i's go to records[offsets[i] .. offsets[i+1]) in the reference's
+ * callback order (a ray reports after its children, the primary ray last: rt_record_rays' order and contents, pad
+ * = 0); rgba_f64 (may be NULL) = get_pixel's colour, 4 doubles per sample, the bits rt_render_points_f64 gives.
+ * n == 0: RT_OK, nothing written.  Memory safety does not depend on the offsets being right: with c = min(cap_records,
+ * offsets[n]), sample i gets the segment [offsets[i], min(offsets[i+1], c)), the empty one when offsets[i] >
+ * offsets[i+1] or offsets[i] > c; records that do not fit are dropped, and no byte outside records[0 .. cap_records)
+ * is ever written.  RT_ERR_INVALID whenever some sample's ray count differs from its segment's length (stale
+ * offsets, another depth, another scene, cap_records below offsets[n]); the samples whose segments were exact then
+ * still hold their correct records (a host buffer's other records are unspecified).  The call returns when its
+ * records are done: it reads offsets[n] first and one small status block (mismatched samples, dropped records) last.
+ * On top of the caller's output the call takes offsets[n] * (160 + 4) bytes of the context's scratch: the records
+ * in start order and their callback-order table, which a second kernel gathers into `records` in 16-byte chunks.
+ * Both calls record the context's timing events (rt_ctx_last_kernel_ms: the call's kernels together) and its
+ * completion mark, and change nothing about later renders (no tile order, no option, rt_ctx_kernel_info's last row
+ * launch), as rt_count_rays and rt_first_hits. */
+int rt_ray_paths_offsets(rt_ctx* ctx, const double* xy, size_t n, int32_t max_depth, uint64_t* offsets,
+                         uint64_t* total, void* stream);
+int rt_ray_paths(rt_ctx* ctx, const double* xy, size_t n, int32_t max_depth, const uint64_t* offsets,
+                 rt_ray_record* records, size_t cap_records, double* rgba_f64, void* stream);
 /* Orthogonal preview view (DebugWindow::render_orthogonal_view_line, debug_window.rs:166-227)
  * for rows [y0, y1) at the scene's W x H: per pixel a ray from 10000 along the third axis with
  * origin[axis1] = ((x - W/2) * dir1) / scale, origin[axis2] = ((y - H/2) * dir2) / scale; the

@@ -7,6 +7,7 @@
                                           [--count-rays] [--ray-map map.png]
                                           [--object-map o.png] [--depth-map d.png] [--normal-map n.png]
                                           [--shadow-map s.png]
+                                          [--ray-paths paths.npz [--ray-paths-step N]]
 
 Replaces the reference's entry point and its GUI load path for this purpose: ``main()`` only
 starts the GTK application (src/main.rs:7-9), which builds a RayTracer per frame with
@@ -80,6 +81,11 @@ def _parse(argv):
     r.add_argument("--shadow-map", default=None, metavar="PATH",
                    help="write the share of the scene's lights each first hit can see as a grey PNG, misses black; "
                         "one GPU, not with --camera anaglyph")
+    r.add_argument("--ray-paths", default=None, metavar="PATH.npz",
+                   help="write the ray debugger's records of the pixel centres of every N-th column and row "
+                        "(rt_ray_paths) as an .npz of xy, offsets and records; one GPU, --camera perspective")
+    r.add_argument("--ray-paths-step", type=int, default=8, metavar="N",
+                   help="the N of --ray-paths (default 8)")
     r.add_argument("-o", "--output", default="out.png")
     a = ap.parse_args(argv)
     for flag in HIT_MAP_FLAGS:
@@ -89,6 +95,13 @@ def _parse(argv):
             ap.error(f"{flag} is not built for --gpus > 1 (no rank holds the whole map)")
         if a.camera == "anaglyph":
             ap.error(f"{flag} is not built for --camera anaglyph (a pixel there has two first hits, one per eye)")
+    if a.ray_paths is not None:
+        if a.gpus > 1:
+            ap.error("--ray-paths is not built for --gpus > 1 (the records are one rank's launch)")
+        if a.camera != "perspective":
+            ap.error(f"--ray-paths is not built for --camera {a.camera} (the recording traces perspective samples)")
+        if a.ray_paths_step < 1:
+            ap.error("--ray-paths-step must be >= 1")
     if a.ray_map is not None:
         if a.gpus > 1:
             ap.error("--ray-map is not built for --gpus > 1 (no rank holds the whole map)")
@@ -166,6 +179,13 @@ def hit_maps(a, planes, n_objects: int, n_lights: int):
             occluded += ((sh >> np.uint64(k)) & np.uint64(1)).astype(np.int64)
         grey = (n_lights - occluded) * 255 // n_lights if n_lights > 0 else np.full(sh.shape, 255, np.int64)
         yield a.shadow_map, np.where(hit, grey, 0).astype(np.uint8)
+
+
+def ray_paths_samples(width: int, height: int, step: int):
+    """--ray-paths' sample positions: the pixel centres of every step-th column and row, row-major, (n, 2) f64."""
+    import numpy as np
+    xs, ys = np.arange(0, width, step, dtype=np.float64), np.arange(0, height, step, dtype=np.float64)
+    return np.stack(np.meshgrid(xs, ys), axis=-1).reshape(-1, 2)
 
 
 def render(a) -> dict:
@@ -268,6 +288,16 @@ def render(a) -> dict:
         hits = {"objects_hit": int(np.unique(planes["object"][planes["object"] >= 0]).size)}
         for path, grey in hit_maps(a, planes, info["objects"], info["lights"]):
             write_png(path, grey if grey.ndim == 3 else np.repeat(grey[..., None], 4, axis=-1), channels=3)
+    paths = None
+    if a.ray_paths is not None:
+        # the ray debugger's records at the pixel centres of every N-th column and row, row-major (one GPU)
+        t0 = time.perf_counter()
+        xy = ray_paths_samples(W, H, a.ray_paths_step)
+        res = r.ray_paths(xy, max_depth=a.depth)
+        paths = {"points": int(xy.shape[0]), "records": int(res["records"].shape[0]),
+                 "ms": round((time.perf_counter() - t0) * 1e3, 3)}
+        with open(a.ray_paths, "wb") as f:     # (a file object: numpy appends no suffix to the path)
+            np.savez(f, xy=xy, offsets=res["offsets"], records=res["records"])
     if rank == 0:
         t0 = time.perf_counter()
         host = frame.cpu().numpy()
@@ -280,7 +310,7 @@ def render(a) -> dict:
     return {"output": a.output, "width": W, "height": H, "time": a.t, "gpus": world,
             **{k: round(v, 3) for k, v in times.items()}, **({"aa_rays": aa_rays} if a.antialias else {}),
             **({"rays": rays, "rays_per_pixel": round(rays["total"] / (W * H), 3)} if rays is not None else {}),
-            **(hits or {})}
+            **(hits or {}), **({"ray_paths": paths} if paths is not None else {})}
 
 
 def main(argv=None) -> int:

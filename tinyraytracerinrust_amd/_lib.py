@@ -142,6 +142,8 @@ SIGNATURES = {
     "rt_trace_pixel_f64": (_I, [_P, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int, _P]),
     "rt_record_rays": (_I, [_P, ctypes.c_double, ctypes.c_double, ctypes.c_int32, _P, ctypes.c_int32,
                             ctypes.POINTER(ctypes.c_int32), _P]),
+    "rt_ray_paths_offsets": (_I, [_P, _P, ctypes.c_size_t, ctypes.c_int32, _P, ctypes.POINTER(ctypes.c_uint64), _P]),
+    "rt_ray_paths": (_I, [_P, _P, ctypes.c_size_t, ctypes.c_int32, _P, _P, ctypes.c_size_t, _P, _P]),
     "rt_render_ortho": (_I, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                              ctypes.c_uint32, ctypes.c_uint32, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P]),
     "rt_antialias": (_I, [_P, _P, ctypes.c_size_t, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _P,

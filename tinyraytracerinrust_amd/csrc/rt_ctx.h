@@ -273,7 +273,7 @@ int finish_calibration(rt_ctx* c, hipStream_t st, rt_ctx::OrderSlot* slot, const
 // memory (the launch rendered into the context's scratch) and the wait for it.
 struct HostCopy { void* out; size_t stride; const uint8_t* src; size_t src_stride, row_bytes, n_rows; };   // out null: none
 int finish_launch(rt_ctx* c, hipStream_t st, const HostCopy& hc, bool mark);
-// The launch bracket of the side entries (k_views.hip, k_points.hip, k_stats.hip, k_hits.hip).  begin_launch: the
+// The launch bracket of the side entries (k_views.hip, k_points.hip, k_stats.hip, k_hits.hip, k_paths.hip).  begin_launch: the
 // timing pair's start event; what an entry keeps out of rt_ctx_last_kernel_ms (memsets of its sums) it enqueues
 // first.  end_launch, behind the entry's last kernel: the launch error, the stop event, the completion mark.
 inline int begin_launch(rt_ctx* c, hipStream_t st) { if (c->timing) RT_HIP(hipEventRecord(c->ev0, st)); return RT_OK; }
@@ -304,7 +304,7 @@ struct Stager {
   enum Kind { OUT, IN, TABLE };
   struct Plane { void* p; size_t stride, row_bytes, n_rows, align; const char* what; Kind kind; bool dev; size_t off; };
   int add(const Plane& q) { pl[n] = q; return n++; }
-  Plane pl[6];                                   // the most an entry has: five (rt_antialias, rt_first_hits_points)
+  Plane pl[6];                                   // the most an entry has: six (rt_ray_paths)
   int n = 0;
   uint8_t* base = nullptr;
   bool staged = false;

@@ -627,6 +627,34 @@ class Renderer:
                                    cap, ctypes.byref(n), rgba))
         return buf[:min(n.value, cap)].copy(), np.array(rgba[:])
 
+    def ray_paths_offsets(self, xy, max_depth: int = -1) -> np.ndarray:
+        """rt_ray_paths_offsets: how many rays each sample position of ``xy`` (n, 2) traces (primary + reflect +
+        refract), as an exclusive prefix sum: a uint64 array of n + 1, the last entry the total.  Synchronous."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        n = xy.shape[0]
+        offsets = np.zeros(n + 1, np.uint64)
+        total = ctypes.c_uint64(0)
+        check(lib().rt_ray_paths_offsets(self.h, ctypes.c_void_p(xy.ctypes.data), n, int(max_depth),
+                                         ctypes.c_void_p(offsets.ctypes.data), ctypes.byref(total), None))
+        return offsets
+
+    def ray_paths(self, xy, max_depth: int = -1) -> dict:
+        """The ray debugger's records of every sample position of ``xy`` (n, 2) in one launch (rt_ray_paths_offsets,
+        then rt_ray_paths into buffers of exactly the total): ``"offsets"`` uint64 (n + 1), ``"records"`` a
+        RAY_RECORD_DTYPE array of offsets[n] records -- sample i's are records[offsets[i]:offsets[i + 1]] in the
+        reference's callback order, the primary ray last -- and ``"rgba"`` (n, 4) float64, get_pixel's colours.
+        Perspective scenes; synchronous."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        n = xy.shape[0]
+        offsets = self.ray_paths_offsets(xy, max_depth)
+        total = int(offsets[n])
+        records = np.zeros(total, RAY_RECORD_DTYPE)
+        rgba = np.zeros((n, 4), np.float64)
+        check(lib().rt_ray_paths(self.h, ctypes.c_void_p(xy.ctypes.data), n, int(max_depth),
+                                 ctypes.c_void_p(offsets.ctypes.data), ctypes.c_void_p(records.ctypes.data), total,
+                                 ctypes.c_void_p(rgba.ctypes.data), None))
+        return {"offsets": offsets, "records": records, "rgba": rgba}
+
     def render_ortho(self, axes: "OrthoAxes", y0: int = 0, y1: Optional[int] = None, f64: bool = False) -> np.ndarray:
         """rt_render_ortho rows [y0, y1) into a host array (uint8 RGBA, or float64 with ``f64``)."""
         y1 = self.height if y1 is None else y1
@@ -948,6 +976,11 @@ class RayTracer:
         res = self.renderer.first_hits_points(np.array([[x, y]], np.float64))
         return int(res["object"][0]), float(res["distance"][0])
 
+    def ray_paths(self, xy) -> dict:
+        """The ray debugger's records of every sample position of ``xy`` (n, 2) at this tracer's max_depth
+        (Renderer.ray_paths): offsets, records in callback order per sample, colours."""
+        return self.renderer.ray_paths(xy, self.max_depth)
+
     def render_orthogonal_view_line(self, y: int, ortho_axes: "OrthoAxes") -> np.ndarray:
         """DebugWindow::render_orthogonal_view_line (debug_window.rs:166-227): (W, 4) f64 colours."""
         return _ortho_line(self, y, ortho_axes)
@@ -981,6 +1014,16 @@ class RayDebugger:
             return
         self.debugged_position = (x, y)
         self.rays = ray_tracer.renderer.record_rays(x, y, ray_tracer.max_depth)[0]
+
+    def record_rays_many(self, ray_tracer: "RayTracer", xy) -> np.ndarray:
+        """record_rays for every sample position of ``xy`` (n, 2) in one launch (RayTracer.ray_paths): ``rays`` then
+        holds every sample's records in sample order, each sample's in callback order -- what the ortho views draw
+        for a scanline or a dragged region.  Returns the offsets (n + 1) of the samples' records in ``rays``."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        res = ray_tracer.ray_paths(xy)
+        self.debugged_position = None if xy.shape[0] != 1 else (float(xy[0, 0]), float(xy[0, 1]))
+        self.rays = res["records"]
+        return res["offsets"]
 
     def reset_debugger(self) -> None:
         self.debugged_position = None
