@@ -45,6 +45,10 @@ CASES = [
     ("spinning_globes", 0.3, 96, 72, 0.01, 3),   # refraction chains
     ("three_cubes", 0.0, 96, 72, 0.01, 3),
     ("fractal", 0.0, 64, 48, 0.01, 3),
+    # the classify kernel's 16x16 tiles: one pixel past a tile in x and in y (the CPU oracle: 302 edge pixels, 2 of
+    # them in column 15, 179 in rows >= 16; 14 015 rays), and exactly one tile (92 edge pixels, 4 851 rays)
+    ("globes", 0.0, 17, 33, 0.01, 3),
+    ("globes", 0.0, 16, 16, 0.01, 3),
 ]
 
 
@@ -55,6 +59,8 @@ def test_antialias_parity(T, worldmap, name, time, W, H, threshold, level):
     assert grays == rrays == grays2
     if level == 0:
         assert grays == 0
+    if W < 64:
+        assert grays > 0                      # the small frames have edge pixels
     fd = np.abs(gf - rf)
     assert fd.max() <= F64_TOL, f"f64 max |d| {fd.max():.3e}"
     d = np.abs(gu.astype(np.int16) - ru.astype(np.int16))
@@ -96,7 +102,10 @@ ORTHO = [("top", (0, 2, 1.0, -1.0)), ("front", (0, 1, 1.0, -1.0)), ("side", (2, 
 
 @pytest.mark.parametrize("name,time,W,H", [("globes", 0.0, 160, 120), ("three_cubes", 0.0, 128, 96),
                                            ("spinning_gimbals", 0.4, 128, 96), ("fractal", 0.0, 96, 72),
-                                           ("ground_star", 0.2, 128, 96)])
+                                           ("ground_star", 0.2, 128, 96),
+                                           # the kernel's 16x16 tiles: one pixel past a tile each way, exactly one
+                                           # tile (the CPU oracle: every pixel of all three views hits an object)
+                                           ("globes", 0.0, 17, 33), ("globes", 0.0, 16, 16)])
 def test_ortho_views_parity(T, worldmap, name, time, W, H):
     """Orthogonal previews (debug_window.rs:166-227) against the oracle: bit-exact (no libm)."""
     from oracle import oracle as O
@@ -109,6 +118,8 @@ def test_ortho_views_parity(T, worldmap, name, time, W, H):
         gu = rt.render_orthogonal_view(area)
         assert np.array_equal(gf, rf), f"{name} {area}: f64 differs"
         assert np.array_equal(gu, ru)
+        if W < 64:
+            assert gu.any()                       # the small frames show the globes in every view
     line = rt.render_orthogonal_view_line(H // 2, T.OrthoAxes.from_area("front"))
     assert np.array_equal(line, ref.render_ortho(0, 1, 1.0, -1.0, 2.0, H // 2, H // 2 + 1)[0][0])
     with pytest.raises(T.RtError):

@@ -238,9 +238,15 @@ def _edge_mask(frame, threshold):
     return mask
 
 
-@pytest.mark.parametrize("threshold", [0.01, 0.0])
-def test_edge_overlay(globes, threshold):
+# size None: the module's 72x53 frame; 17x33: one pixel past the kernel's 16x16 tile in x and in y (the CPU oracle's
+# frame: 302 edge pixels, 179 of them in rows >= 16, 2 in column 15); 16x16: exactly one tile (92 edge pixels)
+@pytest.mark.parametrize("size,threshold", [pytest.param(None, 0.01, id="0.01"), pytest.param(None, 0.0, id="0.0"),
+                                            pytest.param((17, 33), 0.01, id="17x33"),
+                                            pytest.param((16, 16), 0.01, id="16x16")])
+def test_edge_overlay(T, globes, size, threshold):
     import torch
+    if size is not None:
+        globes = Whole(T, "globes", 0.0, size[0], size[1], threshold, 0)
     mask = _edge_mask(globes.frame, threshold)
     mark = np.array([np.uint8(np.float64(c) * 255.0) for c in (0.6, 1.0, 1.0, 0.5)])
     assert mark.tolist() == [153, 255, 255, 127]
@@ -252,7 +258,9 @@ def test_edge_overlay(globes, threshold):
     assert not overlay[-1].any() and not overlay[:, -1].any()
     dev, dn = globes.r.antialias_edges(torch.from_numpy(np.array(globes.frame)).cuda(), threshold)
     assert dev.is_cuda and dn == n and np.array_equal(dev.cpu().numpy(), overlay)
-    if threshold == 0.01:
+    if size == (17, 33):
+        assert mask[16:].any() and mask[:, 15].any()                 # past the first tile row; the tile's last column
+    if size is None and threshold == 0.01:
         assert n == 713 and not mask[:10].any()                      # the CPU oracle's frame: 713 edge pixels, rows 0..9 free
 
 

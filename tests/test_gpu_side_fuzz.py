@@ -1,4 +1,4 @@
-"""The side kernels -- first-hit maps (k_hits.hip), ray counts (k_stats.hip) and the ray recorder (k_views.hip) -- on
+"""The side kernels -- first-hit maps (k_hits.hip), ray counts (k_stats.hip) and the ray recorder (k_paths.hip) -- on
 the inputs the render kernels have long been held to: seeded fuzz scenes (tests/scene_fuzz.py: ray trees, ray chains,
 rod scenes culled with oriented boxes) and the coincident-surface tie scenes, at 64x48 (whole 8x8 tiles) and 60x45
 (a partial tile column and row), depth 6; ray trees at RT_MAX_DEPTH_CAP; a scene of 32 lights, whose last light is

@@ -97,22 +97,21 @@ static void with_hit_flags(bool refr, bool shadow, bool normal, bool views, F&& 
   });
 }
 
-// What every entry checks before its geometry: the context, its scene, the camera kind and the shadow bits' room.
-static int hits_scene_ok(rt_ctx* c, bool shadow) {
-  if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
-  if (c->views.kind == RT_CAMERA_ANAGLYPH)
-    return fail(RT_ERR_UNSUPPORTED, "first hits of an anaglyph scene: a pixel has two, one per eye");
-  if (shadow && c->dev.n_lights > 32)
-    return fail(RT_ERR_UNSUPPORTED, "shadow bits of %d lights > 32", c->dev.n_lights);
+// What every entry checks before its geometry: the side entries' refusals, the camera kind, the shadow bits' room.
+static int hits_scene_ok(rt_ctx* c, bool args, bool shadow) {
+  RT_TRY(side_entry_ok(c, args, nullptr, nullptr));
+  if (c->views.kind == RT_CAMERA_ANAGLYPH) return fail(RT_ERR_UNSUPPORTED, "first hits of an anaglyph scene: a pixel has two, one per eye");
+  if (shadow && c->dev.n_lights > 32) return fail(RT_ERR_UNSUPPORTED, "shadow bits of %d lights > 32", c->dev.n_lights);
   return RT_OK;
 }
 
+extern "C" {
+
 // The rows of a band layout, cut to the frame by clamp_bands (launch_plan.h): the kernel sees n_rows packed rows
 // that all exist.
-static int hits_rows(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
-                     const rt_hit_planes* out, void* stream) {
-  if (!c || !out || (!out->object && !out->distance && !out->shadow && !out->normal)) return fail(RT_ERR_INVALID, "null argument");
-  RT_TRY(hits_scene_ok(c, out->shadow != nullptr));
+int rt_first_hits_row_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
+                            const rt_hit_planes* out, void* stream) {
+  RT_TRY(hits_scene_ok(c, out && (out->object || out->distance || out->shadow || out->normal), out && out->shadow));
   const int W = c->dev.width;
   struct Plane { void* p; size_t stride, px; const char* what; };
   const Plane pl[4] = {{out->object, out->object_stride, 4, "object"}, {out->distance, out->distance_stride, 8, "distance"},
@@ -142,24 +141,15 @@ static int hits_rows(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t b
   return sg.finish(st, false);
 }
 
-extern "C" {
-
-int rt_first_hits_row_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
-                            const rt_hit_planes* out, void* stream) {
-  return hits_rows(c, y_first, band_rows, band_pitch, n_bands, out, stream);
-}
-
 int rt_first_hits(rt_ctx* c, uint32_t y0, uint32_t y1, const rt_hit_planes* out, void* stream) {
-  if (!c || !out || (!out->object && !out->distance && !out->shadow && !out->normal)) return fail(RT_ERR_INVALID, "null argument");
-  if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
+  RT_TRY(side_entry_ok(c, out && (out->object || out->distance || out->shadow || out->normal), nullptr, nullptr));
   if (y0 > y1 || y1 > (uint32_t)c->dev.height) return fail(RT_ERR_INVALID, "bad row range [%u, %u) for height %d", y0, y1, c->dev.height);
-  return hits_rows(c, y0, y1 - y0, y1 - y0, 1, out, stream);
+  return rt_first_hits_row_bands(c, y0, y1 - y0, y1 - y0, 1, out, stream);
 }
 
 int rt_first_hits_points(rt_ctx* c, const double* xy, size_t n, int32_t* object, double* distance, uint32_t* shadow,
                          double* normal, void* stream) {
-  if (!c || !xy || (!object && !distance && !shadow && !normal)) return fail(RT_ERR_INVALID, "null argument");
-  RT_TRY(hits_scene_ok(c, shadow != nullptr));
+  RT_TRY(hits_scene_ok(c, xy && (object || distance || shadow || normal), shadow != nullptr));
   if (n == 0) return RT_OK;
   if (n > (size_t)INT32_MAX) return fail(RT_ERR_INVALID, "%zu sample positions > %d", n, INT32_MAX);
   RT_HIP(hipSetDevice(c->device));

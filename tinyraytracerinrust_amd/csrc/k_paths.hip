@@ -1,6 +1,7 @@
-// k_paths.hip -- the ray debugger's recording for many samples in one launch (rt_ray_paths_offsets, rt_ray_paths;
-// RayDebugger::record_rays, ray_debugger.rs:92-137, over the RayDebuggerCallback of raytracer.rs:17-19): one lane per
-// sample, every sample's records packed into a segment of exactly its size, in the reference's callback order.
+// k_paths.hip -- the ray debugger's recording (RayDebugger::record_rays, ray_debugger.rs:92-137, over the
+// RayDebuggerCallback of raytracer.rs:17-19): of one sample (rt_record_rays: one thread, room for the whole ray tree) and of
+// many in one launch (rt_ray_paths_offsets, rt_ray_paths): one lane per sample, every sample's records packed into a
+// segment of exactly its size, in the reference's callback order.
 //   count   paths_count_kernel: trace() with a recorder of one counter -> uint32 per sample;
 //   scan    scan_*_kernel: the counts' exclusive prefix sum into uint64 offsets (paths_plan.h: three steps, no
 //           workgroup waits for another);
@@ -160,6 +161,21 @@ __global__ __launch_bounds__(256) void paths_fill_kernel(RtDevScene S, const dou
   }
 }
 
+// rt_record_rays: one thread, the same recorder on a table that holds the whole ray tree; get_pixel's colour behind it.
+template <bool REFR>
+__global__ void record_ray_kernel(RtDevScene S, double x, double y, int max_depth, RtRayRecord* rec, int* order,
+                                  int cap, int* counts) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const DS D = make_ds(S);
+  BufRec R{rec, order, cap, 0, 0, &D};
+  V3 ro, rd;
+  camera_ray(S.cam, x, y, &ro, &rd);
+  const Col c = trace<REFR, BufRec>(D, ro, rd, max_depth, &R);
+  counts[0] = R.n_begun;
+  counts[1] = R.n_done;
+  rec[cap].color[0] = c.r; rec[cap].color[1] = c.g; rec[cap].color[2] = c.b; rec[cap].color[3] = 1.0;   // get_pixel's return
+}
+
 // One thread per (record, 16-byte chunk), ten chunks per 160-byte record: out[j] = tmp[order[j]].  Consecutive
 // threads write consecutive 16 bytes.  An entry that is no index into the scratch (never written: its sample's
 // rays did not fill the segment) leaves the output record alone.  Chunk 1 holds rt_ray_record::pad, which no
@@ -182,13 +198,9 @@ __global__ __launch_bounds__(256) void paths_gather_kernel(const uint4* __restri
 
 using namespace rt;
 
-// What both calls check first, in this order: handles, an uploaded perspective scene, the depth, the sample count.
+// What both batched calls check first, in this order: the side entries' refusals for a perspective scene, the sample count.
 static int paths_args_ok(rt_ctx* c, const char* who, const double* xy, size_t n, int32_t* max_depth, ScanPlan* plan) {
-  if (!c) return fail(RT_ERR_INVALID, "null argument");
-  if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
-  if (c->views.kind) return fail(RT_ERR_UNSUPPORTED, "%s is not built for a two-eye scene (stereoscopic / anaglyph camera)", who);
-  if (*max_depth < 0) *max_depth = c->max_depth;
-  if (*max_depth > RT_MAX_DEPTH_CAP) return fail(RT_ERR_UNSUPPORTED, "max_depth %d > %d", *max_depth, RT_MAX_DEPTH_CAP);
+  RT_TRY(side_entry_ok(c, true, who, max_depth));
   *plan = plan_scan(n);
   if (plan->status == ScanPlan::TOO_MANY)
     return fail(RT_ERR_UNSUPPORTED, "%zu sample positions > %llu", n, (unsigned long long)RT_SCAN_MAX_N);
@@ -296,6 +308,42 @@ int rt_ray_paths(rt_ctx* c, const double* xy, size_t n, int32_t max_depth, const
   if (status[0])
     return fail(RT_ERR_INVALID, "%u of %zu samples trace another number of rays than their offsets say (%u records dropped): "
                 "stale offsets, another depth or scene, or cap_records below offsets[n]", status[0], n, status[1]);
+  return RT_OK;
+}
+
+// RayDebugger::record_rays (ray_debugger.rs:92-137): one thread, records in callback order.
+int rt_record_rays(rt_ctx* c, double x, double y, int32_t max_depth, rt_ray_record* records, int32_t cap,
+                   int32_t* n_rays, double* rgba) {
+  RT_TRY(side_entry_ok(c, (records || cap <= 0) && cap >= 0 && n_rays, "rt_record_rays", &max_depth));
+  RT_HIP(hipSetDevice(c->device));
+  // room for the whole ray tree: a chain of max_depth + 1 rays, or a binary tree with refraction
+  const bool refr = c->dev.any_transparent != 0;
+  const int dev_cap = refr ? (2 << max_depth) - 1 : max_depth + 1;
+  const size_t rec_bytes = sizeof(rt_ray_record) * ((size_t)dev_cap + 1);
+  hipStream_t st = nullptr;
+  Stager sg;                                // the recorder's tables: records, their callback order, two counters
+  const int i_rec = sg.add_scratch(rec_bytes), i_ord = sg.add_scratch((size_t)dev_cap * 4), i_cnt = sg.add_scratch(64);
+  RT_TRY(sg.reserve(c, st));
+  rt_ray_record* d_rec = sg.ptr<rt_ray_record>(i_rec);
+  int* d_ord = sg.ptr<int>(i_ord);
+  int* d_cnt = sg.ptr<int>(i_cnt);
+  with_bool(refr, [&](auto R) {
+    hipLaunchKernelGGL((record_ray_kernel<decltype(R)::value>), dim3(1), dim3(64), 0, st, c->dev, x, y, (int)max_depth, d_rec,
+                       d_ord, dev_cap, d_cnt);
+  });
+  RT_HIP(hipGetLastError());
+  RT_TRY(rt::mark_launch(c, st));
+  int cnt[2] = {0, 0};
+  RT_HIP(hipMemcpy(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost));
+  if (cnt[0] != cnt[1] || cnt[1] > dev_cap) return fail(RT_ERR_DEVICE, "ray recorder overflow (%d/%d of %d)", cnt[0], cnt[1], dev_cap);
+  std::vector<rt_ray_record> rec((size_t)dev_cap + 1);
+  std::vector<int> ord((size_t)dev_cap);
+  RT_HIP(hipMemcpy(rec.data(), d_rec, rec_bytes, hipMemcpyDeviceToHost));
+  RT_HIP(hipMemcpy(ord.data(), d_ord, sizeof(int) * (size_t)dev_cap, hipMemcpyDeviceToHost));
+  *n_rays = cnt[1];
+  const int keep = cnt[1] < cap ? cnt[1] : cap;
+  for (int i = 0; i < keep; ++i) records[i] = rec[(size_t)ord[i]];
+  if (rgba) for (int k = 0; k < 4; ++k) rgba[k] = rec[(size_t)dev_cap].color[k];
   return RT_OK;
 }
 

@@ -9,9 +9,6 @@
 #ifndef RT_CULL_F32
 #define RT_CULL_F32 1
 #endif
-#include <stdio.h>
-#include <stdlib.h>
-
 #include "rt_device.h"
 #include "rt_ctx.h"
 
@@ -81,10 +78,7 @@ int rt_trace_pixel_f64(const rt_scene* scene, double x, double y, int32_t max_de
 }
 
 int rt_render_points_f64(rt_ctx* c, const double* xy, size_t n, int32_t max_depth, double* out, void* stream) {
-  if (!c || !xy || !out) return fail(RT_ERR_INVALID, "null argument");
-  if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
-  if (max_depth < 0) max_depth = c->max_depth;
-  if (max_depth > RT_MAX_DEPTH_CAP) return fail(RT_ERR_UNSUPPORTED, "max_depth %d > %d", max_depth, RT_MAX_DEPTH_CAP);
+  RT_TRY(side_entry_ok(c, xy && out, nullptr, &max_depth));
   if (n == 0) return RT_OK;
   RT_HIP(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;   // NULL = the device's default stream
@@ -107,12 +101,11 @@ int rt_render_points_f64(rt_ctx* c, const double* xy, size_t n, int32_t max_dept
     void* kargs[] = {&c->dev, (void*)&in, &n, &depth, &target};
     RT_HIP(hipModuleLaunchKernel(sfn, (unsigned)((n + 63) / 64), 1, 1, 64, 1, 1, 0, st, kargs, nullptr));
   }
-  else if (c->views.kind && c->dev.any_transparent)
-    hipLaunchKernelGGL((render_points_views_kernel<true>), grid, block, 0, st, c->dev, c->views, in, n, max_depth, target);
-  else if (c->views.kind)
-    hipLaunchKernelGGL((render_points_views_kernel<false>), grid, block, 0, st, c->dev, c->views, in, n, max_depth, target);
-  else if (c->dev.any_transparent) hipLaunchKernelGGL((render_points_kernel<true>), grid, block, 0, st, c->dev, in, n, max_depth, target);
-  else hipLaunchKernelGGL((render_points_kernel<false>), grid, block, 0, st, c->dev, in, n, max_depth, target);
+  else
+    with_bool(c->dev.any_transparent != 0, [&](auto R) {
+      if (c->views.kind) hipLaunchKernelGGL((render_points_views_kernel<decltype(R)::value>), grid, block, 0, st, c->dev, c->views, in, n, max_depth, target);
+      else hipLaunchKernelGGL((render_points_kernel<decltype(R)::value>), grid, block, 0, st, c->dev, in, n, max_depth, target);
+    });
   RT_TRY(end_launch(c, st));
   return sg.finish(st, false);
 }

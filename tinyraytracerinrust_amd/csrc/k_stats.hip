@@ -108,15 +108,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RT_WAVES(REF
 
 using namespace rt;
 
+extern "C" {
+
 // The rows of a band layout, cut to the frame by clamp_bands (launch_plan.h): the kernel sees n_rows packed rows
 // that all exist.
-static int count_rows(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
-                      int32_t max_depth, rt_ray_counts* totals, uint64_t* row_counts, uint32_t* pixel_counts,
-                      size_t pixel_stride, void* stream) {
-  if (!c || (!totals && !row_counts && !pixel_counts)) return fail(RT_ERR_INVALID, "null argument");
-  if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
-  if (max_depth < 0) max_depth = c->max_depth;
-  if (max_depth > RT_MAX_DEPTH_CAP) return fail(RT_ERR_UNSUPPORTED, "max_depth %d > %d", max_depth, RT_MAX_DEPTH_CAP);
+int rt_count_rays_row_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
+                            int32_t max_depth, rt_ray_counts* totals, uint64_t* row_counts, uint32_t* pixel_counts,
+                            size_t pixel_stride, void* stream) {
+  RT_TRY(side_entry_ok(c, totals || row_counts || pixel_counts, nullptr, &max_depth));
   const int W = c->dev.width;
   const size_t row16 = (size_t)W * 16;
   if (pixel_counts && pixel_stride < row16) return fail(RT_ERR_INVALID, "pixel stride %zu < %zu", pixel_stride, row16);
@@ -159,21 +158,11 @@ static int count_rows(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t 
   return RT_OK;
 }
 
-extern "C" {
-
-int rt_count_rays_row_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_t band_pitch, uint32_t n_bands,
-                            int32_t max_depth, rt_ray_counts* totals, uint64_t* row_counts, uint32_t* pixel_counts,
-                            size_t pixel_stride_bytes, void* stream) {
-  return count_rows(c, y_first, band_rows, band_pitch, n_bands, max_depth, totals, row_counts, pixel_counts,
-                    pixel_stride_bytes, stream);
-}
-
 int rt_count_rays(rt_ctx* c, uint32_t y0, uint32_t y1, int32_t max_depth, rt_ray_counts* totals, uint64_t* row_counts,
                   uint32_t* pixel_counts, size_t pixel_stride_bytes, void* stream) {
-  if (!c || (!totals && !row_counts && !pixel_counts)) return fail(RT_ERR_INVALID, "null argument");
-  if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
+  RT_TRY(side_entry_ok(c, totals || row_counts || pixel_counts, nullptr, nullptr));
   if (y0 > y1 || y1 > (uint32_t)c->dev.height) return fail(RT_ERR_INVALID, "bad row range [%u, %u) for height %d", y0, y1, c->dev.height);
-  return count_rows(c, y0, y1 - y0, y1 - y0, 1, max_depth, totals, row_counts, pixel_counts, pixel_stride_bytes, stream);
+  return rt_count_rays_row_bands(c, y0, y1 - y0, y1 - y0, 1, max_depth, totals, row_counts, pixel_counts, pixel_stride_bytes, stream);
 }
 
 }  // extern "C"

@@ -6,8 +6,8 @@
 //   order_from_costs  a calibration's tile costs -> the dispatch order and the slot's two choices
 // Two band rules, because two kinds of kernel read a layout.  The row launches (k_rows.hip launch_bands, k_stereo.hip
 // launch_views, k_masks.hip) keep the caller's layout as it is -- band_geometry: their tile orders, masks and
-// records are keyed by it, and the render kernels drop the rows >= H themselves.  The side entries (k_views.hip
-// antialias_rows, k_stats.hip count_rows, k_hits.hip hits_rows) stage and copy back exactly n_rows packed rows, so
+// records are keyed by it, and the render kernels drop the rows >= H themselves.  The side entries (k_aa.hip
+// antialias_rows, k_stats.hip rt_count_rays_row_bands, k_hits.hip rt_first_hits_row_bands) stage and copy back exactly n_rows packed rows, so
 // the host cuts the layout first -- clamp_bands: bands that start at or past H go, the last band ends at H.
 // The callers see rt_device.h and pass its constants in (rt_ctx.hip finish_calibration among them).
 #pragma once

@@ -89,6 +89,14 @@ __device__ __forceinline__ void tile_pixel(unsigned tile, int pix, int width, in
   *x = (int)(tile % tiles_x) * RT_TILE_W + pix % RT_TILE_W;
   *r = (int)(tile / tiles_x) * RT_TILE_H + pix / RT_TILE_W;
 }
+// The frame-sized side kernels (k_aa.hip classify and edges, k_ortho.hip) take 16x16 tiles, row-major over `width`:
+// a workgroup of four waves, wave w the 8x8 quadrant (w & 1, w >> 1).  Thread `thread` of workgroup `block` -> (x, r).
+__device__ __forceinline__ void tile16_pixel(unsigned block, unsigned thread, int width, int* x, int* r) {
+  const int lane = thread & 63, wave = thread >> 6;
+  const int tiles_x = (width + 15) >> 4;
+  *x = ((block % tiles_x) << 4) + ((wave & 1) << 3) + (lane & 7);
+  *r = ((block / tiles_x) << 4) + ((wave >> 1) << 3) + (lane >> 3);
+}
 
 // Output row r of a launch -> its frame row (see above); a launch of one band (every single-GPU frame)
 // skips the per-lane integer division and remainder (a wave-uniform branch).
@@ -121,6 +129,16 @@ __device__ __forceinline__ void store_pixel(uint8_t* row, int x, Col c, int rgb)
     frame_store<PLAIN>((uint8_t)to_u8(c.b), o + 2);
   } else {
     frame_store<PLAIN>(to_u8(c.r) | (to_u8(c.g) << 8) | (to_u8(c.b) << 16) | (255u << 24), (uint32_t*)row + x);
+  }
+}
+// The side kernels' pixel, with an alpha of its own (k_aa.hip, k_ortho.hip): into row `row` of an RGBA8 plane
+// and of an f64 plane, each optional (null) with its stride in bytes; plain stores.
+__device__ __forceinline__ void put_rgba(double r, double g, double b, double a, int x, int row, uint8_t* u8,
+                                         size_t u8_stride, double* f64, size_t f64_stride) {
+  if (u8) ((uint32_t*)(u8 + (size_t)row * u8_stride))[x] = to_u8(r) | (to_u8(g) << 8) | (to_u8(b) << 16) | (to_u8(a) << 24);
+  if (f64) {
+    double* o = (double*)((uint8_t*)f64 + (size_t)row * f64_stride) + (size_t)x * 4;
+    o[0] = r; o[1] = g; o[2] = b; o[3] = a;
   }
 }
 
@@ -505,7 +523,7 @@ constexpr int rows_lds_doubles() {
 // storage of the scene's mode exactly as rows_entry takes it for a non-PRIM launch (frames: the one-wave
 // workgroup's s_frames of rows_lds_doubles<MODE, KL_, KP_>() doubles).  No tile masks: a sample is in no tile.
 // Lane i of the launch traces sample i; lanes past n leave before trace(), as in the generic kernels
-// (k_points.hip render_points_kernel, k_views.hip aa_trace_kernel), whose stores these repeat.
+// (k_points.hip render_points_kernel, k_aa.hip aa_trace_kernel), whose stores these repeat.
 template <int MODE, bool FC, int KL_ = -1, int KP_ = -1>
 __device__ __forceinline__ void points_body(const RtDevScene& S, const double* __restrict__ xy, size_t n, int max_depth,
                                             double* __restrict__ out, lds_f64* frames) {

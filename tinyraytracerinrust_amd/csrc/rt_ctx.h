@@ -2,7 +2,8 @@
 // host halves of the kernel translation units: rt_ctx.hip (create / upload / options / streams),
 // k_rows.hip (the row kernels' launches), k_stereo.hip (two-eye scenes' launches), k_masks.hip (tile masks and
 // dispatch records), k_wavefront.hip (the wavefront path's level kernels and its launch), k_wf_pairs.hip (its pair
-// path), k_views.hip, spec_ctx.hip.  The launches' decisions are launch_plan.h's and wf_plan.h's (pure host code,
+// path), the side entries' units (k_aa.hip, k_ortho.hip, k_assemble.hip, k_points.hip, k_stats.hip, k_hits.hip,
+// k_paths.hip), spec_ctx.hip.  The launches' decisions are launch_plan.h's and wf_plan.h's (pure host code,
 // no HIP); this header holds what they share on the device side: the slot cache, the order
 // slots' acquisition and calibration, the end of a launch, the side entries' bracket and plane stager, the
 // template dispatch.  Host code only.
@@ -273,7 +274,24 @@ int finish_calibration(rt_ctx* c, hipStream_t st, rt_ctx::OrderSlot* slot, const
 // memory (the launch rendered into the context's scratch) and the wait for it.
 struct HostCopy { void* out; size_t stride; const uint8_t* src; size_t src_stride, row_bytes, n_rows; };   // out null: none
 int finish_launch(rt_ctx* c, hipStream_t st, const HostCopy& hc, bool mark);
-// The launch bracket of the side entries (k_views.hip, k_points.hip, k_stats.hip, k_hits.hip, k_paths.hip).  begin_launch: the
+// What the side entries (k_aa.hip, k_ortho.hip, k_points.hip, k_stats.hip, k_hits.hip, k_paths.hip) refuse first, in
+// this order: a null context or argument (args: the entry's other required pointers are there), a context without a
+// scene, a two-eye scene (two_eye: the entry's name where it is not built for one, else null) and the depth
+// (max_depth, null for an entry that takes none or checks something else first: a negative one becomes the context's,
+// and none may pass RT_MAX_DEPTH_CAP, the frames a lane keeps).
+inline int side_depth_ok(const rt_ctx* c, int32_t* max_depth) {
+  if (*max_depth < 0) *max_depth = c->max_depth;
+  if (*max_depth > RT_MAX_DEPTH_CAP) return fail(RT_ERR_UNSUPPORTED, "max_depth %d > %d", *max_depth, RT_MAX_DEPTH_CAP);
+  return RT_OK;
+}
+inline int side_entry_ok(const rt_ctx* c, bool args, const char* two_eye, int32_t* max_depth) {
+  if (!c || !args) return fail(RT_ERR_INVALID, "null argument");
+  if (!c->uploaded) return fail(RT_ERR_INVALID, "no scene uploaded to this context");
+  if (two_eye && c->views.kind)
+    return fail(RT_ERR_UNSUPPORTED, "%s is not built for a two-eye scene (stereoscopic / anaglyph camera)", two_eye);
+  return max_depth ? side_depth_ok(c, max_depth) : RT_OK;
+}
+// The launch bracket of the side entries.  begin_launch: the
 // timing pair's start event; what an entry keeps out of rt_ctx_last_kernel_ms (memsets of its sums) it enqueues
 // first.  end_launch, behind the entry's last kernel: the launch error, the stop event, the completion mark.
 inline int begin_launch(rt_ctx* c, hipStream_t st) { if (c->timing) RT_HIP(hipEventRecord(c->ev0, st)); return RT_OK; }

@@ -2,7 +2,8 @@
 // create / free, scene upload (rt::flatten -> one HBM blob, rt_blob.h), options, own-queue streams, and what
 // the row launches share: the order slots (acquire_order, finish_calibration) and finish_launch; what the side
 // entries share: the host-or-device planes' Stager (their launch bracket is two lines of rt_ctx.h).
-// Host code only; the kernels and their launches live in k_rows.hip, k_stereo.hip, k_wavefront.hip, k_views.hip.
+// Host code only; the kernels and their launches live in k_rows.hip, k_stereo.hip, k_wavefront.hip and the
+// side entries' units (k_aa.hip, k_ortho.hip, k_assemble.hip, ...).
 #include <stdio.h>
 #include <stdlib.h>
 

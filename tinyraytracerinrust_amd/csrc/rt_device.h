@@ -1,6 +1,6 @@
 // rt_device.h -- the gfx950 (MI355X, CDNA4) device core of the TinyRaytracer render path: the
 // reference's per-ray algorithm (get_ray_color and everything it calls) as device functions, shared
-// by every kernel translation unit (k_rows.hip, k_wavefront.hip, k_views.hip, ...) and by the
+// by every kernel translation unit (k_rows.hip, k_wavefront.hip, k_aa.hip, ...) and by the
 // scene-specialised programs that hipRTC compiles at scene upload (their text: spec_text.cpp; RT_SPEC).
 //
 // One thread per pixel; each 64-lane wave owns an 8x8 pixel tile (coherent primary rays,

@@ -1,7 +1,7 @@
 """Per-pass times of the anti-aliasing trace kernels from a kernel trace of `tools/aa_timing.py --ab`
 (rocprofv3 --kernel-trace --output-format csv ... -- python tools/aa_timing.py --ab ...).
 
-A pass of level L launches the trace kernel L times (one launch per subdivision depth, k_views.hip rt_antialias),
+A pass of level L launches the trace kernel L times (one launch per subdivision depth, k_aa.hip rt_antialias),
 so the dispatches of a trace kernel, in start order, repeat with period L.  Prints, per kernel name (the generic
 aa_trace_kernel instantiation, the specialised rt_spec_aa) and pass index, the median duration and the count.
 usage: python tools/aa_passes.py KERNEL_TRACE_CSV [--level 3]"""

@@ -9,7 +9,7 @@ as tools/ab_libs.py does.  Per round every variant runs one anti-aliasing pass o
 with a device synchronisation, and the pass's kernel span from rt_ctx_last_kernel_ms) and --point-launches
 launches of rt_render_points_f64 on --points random positions (device pointers, one event pair around them).
 Prints per variant the median and every sample, and checks that all variants wrote the same bytes.
-usage: python tools/aa_timing.py --ab [--parent LIB] [--config globes4k|globes1080|anim1080] [--threshold 0.01]
+usage: python tools/aa_timing.py --ab [--parent LIB [--parent-samples 0|1]] [--reverse] [--config globes4k|globes1080|anim1080] [--threshold 0.01]
        [--level 3] [--rounds 7] [--points 1000000]
 The per-pass times of the trace kernels come from a kernel trace of such a run (tools/aa_passes.py)."""
 import argparse
@@ -57,7 +57,9 @@ def ab(a):
     scene, t, W, H = CONFIGS[a.config]
     text = open(os.path.join(S, scene + ".scene")).read().encode()
     here = os.path.join(ROOT, "tinyraytracerinrust_amd", "librt_mi355x.so")
-    variants = ([("parent", a.parent, -1)] if a.parent else []) + [("samples 0", here, 0), ("samples 1", here, 1)]
+    variants = ([("parent", a.parent, a.parent_samples)] if a.parent else []) + [("samples 0", here, 0), ("samples 1", here, 1)]
+    if a.reverse:
+        variants.reverse()
     st = torch.cuda.current_stream()
     sp = ctypes.c_void_p(st.cuda_stream)
     g = torch.Generator().manual_seed(1)
@@ -144,6 +146,10 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--ab", action="store_true")
     ap.add_argument("--parent", default="")
+    ap.add_argument("--parent-samples", type=int, default=-1, choices=[-1, 0, 1],
+                    help="RT_OPT_SPEC_SAMPLES for the parent build, set and waited for as for this one (-1: a build without "
+                         "the option; one with it then runs the generic kernels until its own request has compiled)")
+    ap.add_argument("--reverse", action="store_true", help="the variants in the opposite order, within every round")
     ap.add_argument("--config", default="globes4k", choices=sorted(CONFIGS))
     ap.add_argument("--threshold", type=float, default=0.01)
     ap.add_argument("--level", type=int, default=3)
