@@ -496,7 +496,11 @@ int rt_ctx_synchronize(rt_ctx* ctx);
  * would pick the masked megakernel (a measured tile order whose calibration found the launch throughput-bound,
  * records on, a program that holds the lean kernels' check) and the upload has had eight row launches already
  * (until then, and for a host that uploads every frame, the predicate's table); 2 every megakernel launch that
- * reads records; 0 never.  Same
+ * reads records; 0 never.  The table values 1 and 3 take also traces the entries with a pixel on a boxed object:
+ * every lane that hit anything, its shadow words from all boxed objects of the scene (the predicate's words are made
+ * for hits on the plane and are not ANDed in) and its refl word under all ones, and such an entry's r0 carries the
+ * sign bit: the megakernel then reads words 1..5 for every depth-0 hit of the entry.  3: as 2, with that table.
+ * 2 keeps the floor-only form (object entries: the predicate's words, no flag), the A/B partner of 3.  Same
  * pixels.  rt_ctx_kernel_info says "; traced masks: on / off" for the last launch, ahead of "; lean tiles: ...";
  * the sky and lean counts are those of the table that was used.
  * Two-eye scenes (rt_scene_set_camera_kind) always take the view megakernels (k_stereo.hip: one launch over
@@ -540,7 +544,8 @@ int rt_scene_tile_masks(const rt_scene* scene, uint32_t y_first, uint32_t band_r
                         uint32_t n_bands, uint32_t* words, size_t cap_words, int32_t info[4]);
 /* The dispatch records of the last row launch (RT_OPT_TILE_RECORDS; tests, debugging), as its kernels read them:
  * 8 words per entry of the launch's tile order -- x0 (the tile's first column; the sign bit: the entry says
- * lean), r0 (its first output row), then prim, shadow[0..3], refl (an empty prim word: the entry says sky).
+ * lean), r0 (its first output row; the sign bit: the entry's words were traced for every hit, RT_OPT_TRACED_MASKS
+ * 1 / 3), then prim, shadow[0..3], refl (an empty prim word: the entry says sky).
  * Waits for the table's gather (and its check or trace pass), copies min(cap_entries, entries) records and sets
  * *n_entries to the table's entry count.  RT_ERR_INVALID when the last row launch read no records or its table
  * has been dropped since (an upload, or eight newer tables). */

@@ -374,7 +374,7 @@ bool masks_usable(const rt_ctx* c) {
 // else gathered on st, behind the mask fill: mask_slot has put the fill, or a wait for its event, on st
 // already.  Launches on other streams wait for the gather's own event.
 int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const int32_t* d_order, uint64_t order_id,
-                   uint32_t n_entries, bool lean, bool traced, const RtTileRec** table, const void** rslot) {
+                   uint32_t n_entries, bool lean, int traced, const RtTileRec** table, const void** rslot) {
   *table = nullptr;
   if (rslot) *rslot = nullptr;
   const bool sky_fill = c->sky_fill && c->sky_ok;
@@ -412,9 +412,9 @@ int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const 
       // it clears the bit where a reflected ray would hit; the entries that keep it are counted behind it.
       // traced: the trace pass in its place (mode bit 0; bit 1: entries may say lean) -- the gather sets no
       // candidate bits, the pass sets the lean bits and makes more sky entries, so the sky count is taken again
-      // with the lean count.
+      // with the lean count.  Mode bit 2: the entries with a pixel on a boxed object are traced too (form 2).
       const int a0 = ms->key[0], a1 = ms->key[1], a2 = ms->key[2], a3 = ms->key[3];
-      const int mode = traced ? (lean ? 3 : 1) : 0;
+      const int mode = traced ? (lean ? 3 : 1) | (traced == 2 ? 4 : 0) : 0;
       RtTileRec* d_recs = slot->d_recs;
       void* kargs[] = {&c->dev, (void*)&a0, (void*)&a1, (void*)&a2, (void*)&a3, &d_recs, (void*)&mode, (void*)&keep_bit};
       RT_HIP(hipModuleLaunchKernel(spec_fn(c, SPEC_LEAN_CHECK, false, false), n_entries, 1, 1, 64, 1, 1, 0, st, kargs, nullptr));

@@ -118,7 +118,8 @@ static int launch_bands(rt_ctx* c, uint32_t y_first, uint32_t band_rows, uint32_
   const RtTileRec* recs = nullptr;
   const void* rec_slot = nullptr;
   if (plan.masks) RT_TRY(mask_slot(c, st, a0, a1, a2, a3, n_tiles, &ms));
-  if (plan.records) RT_TRY(launch_records(c, st, ms, order, order ? slot->order_id : 0, grid.x, plan.lean, plan.traced, &recs,
+  if (plan.records) RT_TRY(launch_records(c, st, ms, order, order ? slot->order_id : 0, grid.x, plan.lean,
+                                        plan.traced ? (plan.traced_objects ? 2 : 1) : 0, &recs,
                                         &rec_slot));
   const uint32_t* masks = ms ? ms->d_masks : nullptr;
   c->last_masked = plan.masks;

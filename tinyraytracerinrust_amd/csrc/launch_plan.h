@@ -137,7 +137,7 @@ struct LaunchFacts {
   bool pool_byte_index;           // RT_POOL_OBJ_INDEX
   // lean tiles: RT_OPT_LEAN_TILES, and the program holds the lean kernel for this f64 and its check
   bool lean_tiles = false, has_lean = false;
-  // traced tile masks: RT_OPT_TRACED_MASKS 0 / 1 / 2, and the program holds the pass (the check kernel: has_check)
+  // traced tile masks: RT_OPT_TRACED_MASKS 0 / 1 / 2 / 3, and the program holds the pass (the check kernel: has_check)
   int traced_masks = 0;
   bool has_check = false;
   uint32_t launches_since_upload = 0;   // row launches of this context since rt_ctx_upload, this one not counted
@@ -160,6 +160,8 @@ struct LaunchPlan {
   bool lean = false;
   // the records' words come from the trace pass (rt_bodies.h trace_masks_body), which also sets the lean bits
   bool traced = false;
+  // ... and the pass also traces the entries with a pixel on a boxed object and flags them (RT_OPT_TRACED_MASKS 1 / 3)
+  bool traced_objects = false;
 };
 
 inline LaunchPlan plan_row_launch(const LaunchFacts& f) {
@@ -245,11 +247,15 @@ inline LaunchPlan plan_row_launch(const LaunchFacts& f) {
   // -- a measured order whose calibration found the launch throughput-bound -- and only once the upload has been
   // rendered RT_TRACED_MIN_LAUNCHES times (the break-even: a host that stops there has paid at most twice the
   // cheaper choice; a host that uploads every frame, the reference's GUI, never pays); until then the launch reads
-  // the predicate's table.  2: every megakernel launch that takes records.  The words hold for the megakernel's
+  // the predicate's table.  2 and 3: every megakernel launch that takes records.  The words hold for the megakernel's
   // pixels; the calibrating kernel renders every tile and the primary-ray kernel keeps the predicate's words.
-  const bool want_traced = f.traced_masks == 2 || (f.traced_masks == 1 && ordered && f.masks_pay &&
+  // The table's form: 1 and 3 take the one whose entries with a pixel on a boxed object are traced as well (their
+  // shadow and refl words, and the flag that lets trace() read them); 2 keeps the floor-only form, whose object
+  // entries hold the predicate's words and no flag -- the same-library A/B partner of 3.
+  const bool want_traced = f.traced_masks == 2 || f.traced_masks == 3 || (f.traced_masks == 1 && ordered && f.masks_pay &&
                                                    f.launches_since_upload >= RT_TRACED_MIN_LAUNCHES);
   p.traced = want_traced && f.has_check && p.path == LaunchPlan::MEGA && p.kind == SPEC_ROWS && p.records && !calibrate;
+  p.traced_objects = p.traced && f.traced_masks != 2;
   // a megakernel launch without a table runs the program's mask-free megakernel (SPEC_ROWS_NOMASK)
   if (p.kind == SPEC_ROWS && !p.masks && f.has[SPEC_ROWS_NOMASK]) p.kind = SPEC_ROWS_NOMASK;
   // With the scene-specialised megakernel loaded for these launches its costliest tiles finish so

@@ -51,6 +51,9 @@ using __hip_internal::uint64_t;
 // row (no division in the kernel) and the tile's mask words.  A calibrating launch has no order: its entry e
 // is tile e, so the record holds no tile index.  An empty prim word (mask[0] == 0) marks a sky tile: the wave
 // stores BLACK and returns (RT_OPT_SKY_FILL; with the option off the gather leaves no prim word empty).
+// The sign bit of x0 says the entry is lean (RT_OPT_LEAN_TILES); the sign bit of r0 (RT_OPT_TRACED_MASKS 1 / 3, set
+// by the trace pass on an entry with a pixel on a boxed object) says words 1..5 hold for every depth-0 hit of the
+// entry, not only for hits on the mask plane.  The kernels mask both off at the record load.
 // Entry e's record is records[e]: four consecutive workgroups
 // share a 128-byte line.  (A layout that gives each XCD's workgroups -- e, e + 8, ... -- a contiguous run was
 // measured equal, DESIGN.md section 7, and cost the kernel an argument and a multiply.)

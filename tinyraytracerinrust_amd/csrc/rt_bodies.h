@@ -211,8 +211,17 @@ __device__ __forceinline__ void rows_entry(const RtDevScene& S, unsigned entry, 
     if constexpr (rt_spec::LEAN_OK && !CAL && !PRIM && MODE == RT_MODE_REFL)
       if (R->x0 < 0) return;
 #endif
+    int r0 = R->r0;
+#if defined(RT_SPEC) && RT_TILE_MASKS
+    // An entry traced for every hit (RT_OPT_TRACED_MASKS 1 / 3; trace_masks_body `objects`): the record's r0 carries
+    // the sign bit, one scalar more for trace().  Only this kernel's tables carry it, as with the lean bit above.
+    if constexpr (rt_spec::LEAN_OK && !CAL && !PRIM && MODE == RT_MODE_REFL) {
+      tm.hit_min = r0 < 0 ? 0x7fffffff : 0;
+      r0 &= 0x7fffffff;
+    }
+#endif
     x = R->x0 + lane % RT_TILE_W;
-    r = R->r0 + lane / RT_TILE_W;
+    r = r0 + lane / RT_TILE_W;
     for (int k = 0; k < RT_TILEMASK_WORDS; ++k) tm.w[k] = R->mask[k];
 #if defined(RT_SPEC) && RT_TILE_MASKS
     // A sky tile (RT_OPT_SKY_FILL): the record's prim word is empty -- no boxed object in the tile's cone, and
@@ -325,8 +334,9 @@ __device__ __forceinline__ void lean_body(const RtDevScene& S, int y_first, int 
 //              an empty word gets where no record may say sky, as the gather has it).  A walk over a subset that
 //              holds each lane's winner returns that winner: the running best is the first object in walk order
 //              that attains the minimum, and a subset keeps the relative order.
-//   An entry in which a lane hits a boxed object stops here: the kernels read its other words under all ones
-//   (trace(): plane_tile is false), so they stay the predicate's.  Else every hit is on the mask plane, and
+//   An entry in which a lane hits a boxed object stops here unless `objects` (below): the kernels read its other
+//   words under all ones (trace(): plane_tile is false), so they stay the predicate's.  Else every hit is on the
+//   mask plane, and
 //   shadow[l]  for each boxed object o of the record's word the shadow walk runs under the one-bit mask 1 << o (the
 //              plane ignores masks and is always walked); bit o stays where some lane's result for that walk
 //              alone is 0.  These programs hold no transparent object (LEAN_OK), so the shadow product is
@@ -335,6 +345,14 @@ __device__ __forceinline__ void lean_body(const RtDevScene& S, int y_first, int 
 //   refl       the lanes that spawn a ray (refl != 0, seen from outside) trace it under the record's refl word; the
 //              new word is the OR of 1 << oi over them, the plane's bit included (prim's argument); lanes that
 //              spawn nothing contribute nothing.
+// objects (RT_OPT_TRACED_MASKS 1 and 3): an entry with a pixel on a boxed object is traced too, with every lane that
+// hit anything, plane or object -- the lanes trace() carries past `if (oi >= 0)`.  The predicate's shadow and refl
+// words are made for hits on the mask plane (an object's far side is occluded by the object itself, whether or
+// not its box shadows the floor under the tile), so here they are neither the candidates nor ANDed in: a shadow
+// word's candidates are all boxed objects of the scene -- one walk under all of them first, and the one-bit walks
+// only where some lane's result is 0 -- and the depth-1 ray is traced under all ones.  The entry's r0 then gets
+// the sign bit (RtTileRec): its words 1..5 hold for every depth-0 hit, and trace() reads them as it does a floor
+// tile's.  The arguments are the ones above; sky and lean entries come out the same either way.
 // Lane exits mirror trace()'s, so each walk runs with the lanes it has there.  The first lane left writes the
 // words (vector stores) and the lean bit of x0 where lean_on: prim is the plane alone, no shadow word of the
 // scene's lights holds a boxed bit, refl is empty -- lean_check_body's own condition (no reflected ray accepts
@@ -346,7 +364,8 @@ __device__ __forceinline__ void lean_body(const RtDevScene& S, int y_first, int 
 // formed).
 template <bool FC>
 __device__ __forceinline__ void trace_masks_body(const RtDevScene& S, int y_first, int band_rows, int band_pitch, int n_rows,
-                                                 RtTileRec* __restrict__ recs, bool lean_on, uint32_t keep_bit) {
+                                                 RtTileRec* __restrict__ recs, bool lean_on, uint32_t keep_bit,
+                                                 bool objects = false) {
   constexpr bool SHARE = false, OBB = true;                                // trace<false>'s walks
   constexpr int plane = rt_spec::MASK_PLANE;
   constexpr uint32_t plane_bit = plane >= 0 ? 1u << (plane & 31) : 0u;
@@ -355,14 +374,14 @@ __device__ __forceinline__ void trace_masks_body(const RtDevScene& S, int y_firs
   RtTileRec* const R = recs + blockIdx.x;
   uint32_t w[RT_TILEMASK_WORDS];
   for (int k = 0; k < RT_TILEMASK_WORDS; ++k) w[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)R->mask[k]);
-  const int x0 = __builtin_amdgcn_readfirstlane(R->x0) & 0x7fffffff, r0 = __builtin_amdgcn_readfirstlane(R->r0);
+  const int x0 = __builtin_amdgcn_readfirstlane(R->x0) & 0x7fffffff, r0 = __builtin_amdgcn_readfirstlane(R->r0) & 0x7fffffff;
   if (w[0] == 0) return;                                                   // sky already
   const int x = x0 + lane % RT_TILE_W, r = r0 + lane / RT_TILE_W;
   if (x >= S.width || r >= n_rows) return;
   const int y = band_row(r, y_first, band_rows, band_pitch, n_rows);
   if (y >= S.height) return;                                               // (an entry without a pixel keeps its record)
-  // the words and x0 as the first lane still here writes them; every operand is wave-uniform
-  auto put = [&](uint32_t prim, bool rest, uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3, uint32_t refl) RT_INL {
+  // the words, x0 and r0 as the first lane still here writes them; every operand is wave-uniform
+  auto put = [&](uint32_t prim, bool rest, uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3, uint32_t refl, bool flag) RT_INL {
     if (lane != (int)__builtin_ctzll(__ballot(true))) return;
     R->mask[0] = prim;
     if (!rest) return;
@@ -374,6 +393,7 @@ __device__ __forceinline__ void trace_masks_body(const RtDevScene& S, int y_firs
     }
     R->mask[5] = refl;
     R->x0 = lean ? x0 | (int32_t)0x80000000u : x0;
+    if (flag) R->r0 = r0 | (int32_t)0x80000000u;
   };
   V3 ro, rd;
   camera_ray_px(S, x, y, &ro, &rd);
@@ -385,11 +405,17 @@ __device__ __forceinline__ void trace_masks_body(const RtDevScene& S, int y_firs
     if (__ballot(oi == o) != 0) prim |= 1u << o;
   prim &= w[0];
   if (prim == 0) prim = keep_bit;
-  if (__ballot(oi >= 0 && oi != plane) != 0 || __ballot(oi >= 0) == 0) {    // a boxed object's pixel, or sky: prim alone
-    put(prim, false, 0u, 0u, 0u, 0u, 0u);
+  const bool obj = __ballot(oi >= 0 && oi != plane) != 0;                  // a pixel on a boxed object
+  if ((obj && !objects) || __ballot(oi >= 0) == 0) {                       // such an entry untraced, or sky: prim alone
+    put(prim, false, 0u, 0u, 0u, 0u, 0u, false);
     return;
   }
   if (oi < 0) return;                                                      // a lane that missed takes no part in what follows
+  // an object entry's words start from every object, a floor-only entry's from the predicate's
+  if (obj) {
+    w[1] = w[2] = w[3] = w[4] = plane_bit | boxed;
+    w[5] = 0xffffffffu;
+  }
   const V3 p = add(ro, scale(rd, t_hit));
   uint32_t sh[4] = {w[1], w[2], w[3], w[4]};
   _Pragma("unroll 1") for (int k = 0; k < rt_spec::N_LIGHTS && k < 4; ++k) {
@@ -401,6 +427,8 @@ __device__ __forceinline__ void trace_masks_body(const RtDevScene& S, int y_firs
     const int ks = __builtin_amdgcn_readfirstlane(k);
     const uint32_t wk = ks == 0 ? w[1] : ks == 1 ? w[2] : ks == 2 ? w[3] : w[4];
     uint32_t todo = wk & boxed, occ = 0;
+    // an object entry: one walk under every candidate first; no lane occluded: no one-bit walk
+    if (obj && todo != 0 && __ballot(shadow_transparency<SHARE, OBB>(ds, p, sdir, ll, todo) == 0.0) == 0) todo = 0;
     _Pragma("unroll 1") while (todo != 0) {
       const uint32_t bit = (uint32_t)__builtin_amdgcn_readfirstlane((int)(todo & (0u - todo)));
       todo ^= bit;
@@ -416,7 +444,7 @@ __device__ __forceinline__ void trace_masks_body(const RtDevScene& S, int y_firs
   // trace<false> at depth 0 (max_depth > 0): a reflection where rp = refl != 0 and the hit is seen from outside
   const bool spawn = refl != 0.0 && !hit_inside(rd, nrm, nlen);
   if (__ballot(spawn) == 0) {
-    put(prim, true, sh[0], sh[1], sh[2], sh[3], 0u);
+    put(prim, true, sh[0], sh[1], sh[2], sh[3], 0u, obj);
     return;
   }
   if (!spawn) return;
@@ -425,17 +453,18 @@ __device__ __forceinline__ void trace_masks_body(const RtDevScene& S, int y_firs
   uint32_t rw = 0;
   for (int o = 0; o < rt_spec::N_OBJECTS && o < 32; ++o)
     if (__ballot(o1 == o) != 0) rw |= 1u << o;
-  put(prim, true, sh[0], sh[1], sh[2], sh[3], rw & w[5]);
+  put(prim, true, sh[0], sh[1], sh[2], sh[3], rw & w[5], obj);
 }
 // The check (k_masks.hip launch_records, behind the gather and ahead of the table's `ready` event): one wave
 // per entry; a candidate entry in which any valid pixel's reflected ray hits loses its bit.
 // mode (wave-uniform): 0 the check; bit 0 the trace pass above in its place (one kernel: each kernel more costs
-// a program 7-9 s of cold compile), bit 1 with it: the table's launches run the lean kernel, entries may say lean.
+// a program 7-9 s of cold compile), bit 1 with it: the table's launches run the lean kernel, entries may say lean;
+// bit 2 with it: entries with a pixel on a boxed object are traced too (`objects`).
 template <bool FC>
 __device__ __forceinline__ void lean_check_body(const RtDevScene& S, int y_first, int band_rows, int band_pitch, int n_rows,
                                                 RtTileRec* __restrict__ recs, int mode = 0, uint32_t keep_bit = 0u) {
   if (__builtin_amdgcn_readfirstlane(mode) != 0) {
-    trace_masks_body<FC>(S, y_first, band_rows, band_pitch, n_rows, recs, (mode & 2) != 0, keep_bit);
+    trace_masks_body<FC>(S, y_first, band_rows, band_pitch, n_rows, recs, (mode & 2) != 0, keep_bit, (mode & 4) != 0);
     return;
   }
   const int lane = threadIdx.x & 63;

@@ -119,7 +119,8 @@ struct rt_ctx {
     bool lean = false;                // gathered with the lean bits and checked (RT_OPT_LEAN_TILES); the entries that
                                       //   kept theirs follow the sky count: d_sky / h_sky [1] their number, [2] ~first
                                       //   entry, [3] last entry + 1 (both 0: none)
-    bool traced = false;              // its words and lean bits are the trace pass's (RT_OPT_TRACED_MASKS)
+    int traced = 0;                   // its words and lean bits are the trace pass's (RT_OPT_TRACED_MASKS): 1 the
+                                      //   floor-only entries', 2 the entries with an object pixel too (r0's flag)
     uint32_t n_entries = 0;           // order entries = records
     uint64_t last_use = 0;
     hipStream_t fill_stream = nullptr;
@@ -147,7 +148,8 @@ struct rt_ctx {
   const void* last_lean_slot = nullptr;
   uint64_t last_lean_id = 0;
   // Traced tile masks (rt_ctx_set_option(RT_OPT_TRACED_MASKS), rt_bodies.h trace_masks_body): 0 never, 1 where the
-  // masked megakernel runs by the library's own choice (LaunchPlan::traced), 2 every megakernel launch with records.
+  // masked megakernel runs by the library's own choice (LaunchPlan::traced), 2 / 3 every megakernel launch with records;
+  // 2 takes the floor-only form of table, 1 and 3 the form whose object entries are traced too (LaunchPlan::traced_objects).
   // last_traced: the last row launch's table was traced; last_rec_*: that table, whatever it holds
   // (rt_ctx_tile_records).
   int traced_masks = 1;
@@ -342,9 +344,10 @@ int mask_slot(rt_ctx* c, hipStream_t st, int a0, int a1, int a2, int a3, size_t 
 // where a tile fails it, both on st ahead of the table's event; the context holds that kernel (LaunchPlan::lean).
 // traced: the same kernel's trace pass instead (RT_OPT_TRACED_MASKS, LaunchPlan::traced): it narrows every entry's
 // words to what its pixels' rays hit and sets the lean bits itself (lean: entries may say lean); the sky and lean
-// counts are taken behind it.
+// counts are taken behind it.  traced: 0 no pass, 1 the floor-only entries, 2 the entries with an object pixel too
+// (LaunchPlan::traced_objects); a table is keyed by the form.
 int launch_records(rt_ctx* c, hipStream_t st, const rt_ctx::MaskSlot* ms, const int32_t* d_order, uint64_t order_id,
-                   uint32_t n_entries, bool lean, bool traced, const RtTileRec** table, const void** rslot = nullptr);
+                   uint32_t n_entries, bool lean, int traced, const RtTileRec** table, const void** rslot = nullptr);
 void drop_records(rt_ctx* c);                  // every record table (upload, free)
 // How many of a record table's entries say sky (rslot as launch_records gave it, rec_id its RecSlot::rec_id);
 // -1: the table has been dropped since, -2: its gather has not completed yet.  Never waits.

@@ -512,7 +512,7 @@ int rt_ctx_set_option(rt_ctx* c, int32_t option, int32_t value) {
     return RT_OK;
   }
   if (option == RT_OPT_TRACED_MASKS) {
-    if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "RT_OPT_TRACED_MASKS value %d", value);
+    if (value < 0 || value > 3) return fail(RT_ERR_INVALID, "RT_OPT_TRACED_MASKS value %d", value);
     c->traced_masks = value;             // record tables are keyed by what a launch takes: the next one gathers its own
     return RT_OK;
   }

@@ -280,10 +280,15 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t m) {                 // s
 
 // A wave's tile-mask words (rt_tilemask.h) as trace() takes them: wave-uniform values the caller read with
 // the wave's dispatch record (rows_entry), scalar registers for the whole trace; all ones without a table.
-struct TileMask { uint32_t w[RT_TILEMASK_WORDS]; };
+// hit_min: the record's flag (RtTileRec r0's sign bit: words 1..5 hold for every depth-0 hit of the wave) as the
+// scalar trace()'s depth-0 ballot compares hit objects with -- 0, or INT32_MAX where the flag is set, so that no
+// hit counts as off the plane.  (The flag as a boolean ORed to the ballot's result cost the 4K globes megakernel
+// two spilled VGPRs; as the ballot's own operand, none.)
+struct TileMask { uint32_t w[RT_TILEMASK_WORDS]; int32_t hit_min; };
 __device__ __forceinline__ TileMask tile_mask_ones() {
   TileMask m;
   for (int k = 0; k < RT_TILEMASK_WORDS; ++k) m.w[k] = 0xffffffffu;
+  m.hit_min = 0;
   return m;
 }
 
@@ -372,7 +377,8 @@ RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, ld
   // gave back 1.6 % of the 4K frame).  Reflection-only kernels: every hit spawns at most
   // one ray and a lane that spawns none leaves the loop, so iteration k traces the depth-k rays of the lanes still here.  The depth-0
   // nearest hit takes `prim`; where every lane that hit something hit the mask plane (one ballot, kept
-  // in a scalar), light l's depth-0 shadow walk takes shadow[l] and the depth-1 nearest hit `refl`;
+  // in a scalar) or the wave's record says its words were traced for every hit (tm.hit_min, the ballot's own
+  // operand), light l's depth-0 shadow walk takes shadow[l] and the depth-1 nearest hit `refl`;
   // every other walk takes all ones.  One walk either way: the mask is an operand, not a second copy.
 #if defined(RT_SPEC) && RT_TILE_MASKS
   constexpr bool MASKS = !REFR && same_type<Rec, NoRec>::value;
@@ -381,7 +387,9 @@ RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, ld
   constexpr bool MASKS = false;
   constexpr int mask_plane = -1;
 #endif
-  [[maybe_unused]] bool plane_tile = false;   // depth 0: every hit of the wave is on the mask plane
+  // depth 0: the wave's shadow[l] and refl words hold for its hits -- every hit is on the mask plane (what the
+  // predicate's words are made for), or the record says its words were traced for every hit (tm.hit_min)
+  [[maybe_unused]] bool plane_tile = false;
   double fA[RT_MAX_DEPTH_CAP][3];     // parent colour already intensified by (1 - w)
   double fW[RT_MAX_DEPTH_CAP];        // child weight w (transparency or reflectivity)
   constexpr bool POOL = KP > 0 && !(REFR && !CHAIN) && same_type<Rec, NoRec>::value;
@@ -490,7 +498,7 @@ RT_FN Col trace(const DS& S, V3 ro, V3 rd, int max_depth, Rec* rec = nullptr, ld
     // no lane re-enters -- the bounce loop never restarts a pixel.  A change that lets a lane take a second
     // primary ray inside this loop must clear plane_tile with it.)
     if constexpr (MASKS)
-      if (iter == 0) plane_tile = mask_plane >= 0 && __ballot(oi >= 0 && oi != mask_plane) == 0;
+      if (iter == 0) plane_tile = mask_plane >= 0 && __ballot(oi >= tm.hit_min && oi != mask_plane) == 0;
     const V3 p = add(ro, scale(rd, t_hit));                               // :162
     if constexpr (RECORD) slot = rec->begin(depth, ray_type, ro, rd, t_hit, oi, p);
     V3 nrm = {0.0, 0.0, 0.0};

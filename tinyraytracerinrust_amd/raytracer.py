@@ -732,13 +732,15 @@ class Renderer:
     def set_traced_masks(self, mode: int) -> None:
         """rt_ctx_set_option(RT_OPT_TRACED_MASKS): a record table's words narrowed once to what its entries' own
         pixels hit, by a trace pass behind the gather (same pixels): 0 never, 1 (the default) where the library
-        itself picks the masked megakernel and the upload has had eight row launches, 2 for every megakernel
-        launch that reads records."""
+        itself picks the masked megakernel and the upload has had eight row launches, 2 and 3 for every megakernel
+        launch that reads records.  The table of 1 and 3 also traces the entries with a pixel on a boxed object
+        (r0's sign bit in ``tile_records``); 2 keeps those entries' predicate words."""
         check(lib().rt_ctx_set_option(self.h, _lib.RT_OPT_TRACED_MASKS, int(mode)))
 
     def tile_records(self) -> np.ndarray:
         """rt_ctx_tile_records: the dispatch records of the last row launch as its kernels read them, uint32
-        [entries, 8]: x0 (sign bit: the entry says lean), r0, prim, shadow[0..3], refl."""
+        [entries, 8]: x0 (sign bit: the entry says lean), r0 (sign bit: words 1..5 traced for every hit), prim,
+        shadow[0..3], refl."""
         n = ctypes.c_uint32()
         check(lib().rt_ctx_tile_records(self.h, None, 0, ctypes.byref(n)))
         recs = np.zeros((n.value, 8), dtype=np.uint32)

@@ -7,7 +7,7 @@ usage: python tools/ab_libs.py LIB [LIB ...] [--config sphere1080d0|globes1080d5
        [--records=-1,1,0] per library: RT_OPT_TILE_RECORDS (-1: leave it)
        [--sky=-1,1,0]     per library: RT_OPT_SKY_FILL (-1: leave it)
        [--lean=-1,1,0]    per library: RT_OPT_LEAN_TILES (-1: leave it)
-       [--traced=-1,1,0,2] per library: RT_OPT_TRACED_MASKS (-1: leave it, for libraries without the option)"""
+       [--traced=-1,1,0,2,3] per library: RT_OPT_TRACED_MASKS (-1: leave it, for libraries without the option)"""
 import argparse
 import ctypes
 import os

@@ -50,7 +50,10 @@ def stats(name):
 def truth(name):
     """--truth: the predicate's classes against what the pixel centres' own rays do, from the CPU oracle alone
     (orc_hit_signature per pixel: the object hit and the occluded lights; record_rays on floor pixels: the depth-1
-    ray's hit) -- the bound on what a table traced per entry (RT_OPT_TRACED_MASKS) can reclassify."""
+    ray's hit) -- the bound on what a table traced per entry (RT_OPT_TRACED_MASKS) can reclassify.  And the object
+    tiles (a pixel on a boxed object; RT_OPT_TRACED_MASKS 1 / 3 trace them too, with every pixel that hits anything):
+    those with no occluded pixel per light and for every light, the objects their depth-1 rays hit, and those whose
+    pixels spawn no depth-1 ray -- the bound the device's words of flagged entries are compared with."""
     import tinyraytracerinrust_amd as T
     from oracle import oracle as O
     scene, W, H = CONFIGS[name]
@@ -66,6 +69,9 @@ def truth(name):
     hit = np.zeros(tx * ty, bool)                    # ... a pixel that hits anything
     occl = np.zeros((n_lights, tx * ty), bool)       # ... a floor pixel whose light l is occluded
     refl = np.zeros(tx * ty, bool)                   # ... a floor pixel whose depth-1 ray hits
+    o_occl = np.zeros((n_lights, tx * ty), bool)     # ... a pixel, floor or object, whose light l is occluded
+    o_refl = np.zeros(tx * ty, np.uint32)            # the objects hit by the depth-1 rays of the tile's pixels
+    o_spawn = np.zeros(tx * ty, bool)                # ... a pixel that spawns a depth-1 ray
     for y in range(H):
         for x in range(W):
             sig = orc.hit_signature(x, y)
@@ -73,6 +79,9 @@ def truth(name):
                 continue
             t = (y // 8) * tx + x // 8
             hit[t] = True
+            for l in range(n_lights):
+                if (sig // 4096 >> l) & 1:
+                    o_occl[l, t] = True
             if sig % 4096 - 1 != plane:
                 obj[t] = True
                 continue
@@ -83,6 +92,17 @@ def truth(name):
                 r = orc.record_rays(x, y, cap=4)[0].view(T.RAY_RECORD_DTYPE)
                 refl[t] = bool(((r["depth"] == 1) & (r["intersected"] != 0)).any())
     floor_t = hit & ~obj                             # every hit of the tile is on the floor
+    for t in np.flatnonzero(obj):                    # the object tiles' depth-1 rays, every pixel that hits anything
+        for y in range((t // tx) * 8, min((t // tx) * 8 + 8, H)):
+            for x in range((t % tx) * 8, min((t % tx) * 8 + 8, W)):
+                if orc.hit_signature(x, y) < 0:
+                    continue
+                r = orc.record_rays(x, y, cap=4)[0].view(T.RAY_RECORD_DTYPE)
+                d1 = r[r["depth"] == 1]
+                if len(d1):
+                    o_spawn[t] = True
+                    if d1[0]["intersected"]:
+                        o_refl[t] |= np.uint32(1) << np.uint32(d1[0]["object"])
     p_sky = words[:, 0] == 0
     p_prim = (words[:, 0] & boxed) != 0
     p_floor = ~p_sky & ~p_prim
@@ -101,6 +121,13 @@ def truth(name):
     print(f"  lean tiles (predicate candidates): {p_lean.sum()} | {(unshadowed & ~refl).sum()} are all floor, unshadowed and no "
           f"depth-1 ray hits; {unshadowed.sum()} are all floor and unshadowed, {(unshadowed & ((words[:, 5] & boxed) != 0)).sum()} of "
           f"those have a boxed bit in refl")
+    n_obj = int(obj.sum())
+    print(f"  object tiles: {n_obj}; no pixel occluded: " +
+          ", ".join(f"light {l} {(obj & ~o_occl[l]).sum()} ({100.0 * (obj & ~o_occl[l]).sum() / max(1, n_obj):.0f} %)" for l in range(n_lights)) +
+          f", every light {(obj & ~o_occl.any(axis=0)).sum()} ({100.0 * (obj & ~o_occl.any(axis=0)).sum() / max(1, n_obj):.0f} %)")
+    bits = np.array([bin(int(v)).count("1") for v in o_refl[obj]])
+    print(f"  object tiles: objects hit by depth-1 rays, mean per tile {bits.mean() if n_obj else 0.0:.3f} (the plane included); "
+          f"every pixel spawns no depth-1 ray on {(obj & ~o_spawn).sum()} tiles")
 
 
 if __name__ == "__main__":
